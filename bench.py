@@ -25,12 +25,24 @@ frames (default no early stop, the driver's MaxBlock branch; `--mc-stop 1000`
 sharded over the ranks by global frame id (montecarlo.run_point), and reports
 BER/BLER plus the end-to-end rate (generate + decode + count).
 
-Rank 0 prints one JSON line (contract in the task statement), including
-`roofline` for the decode kernel (HIP events around each of its launches on
-the launch stream; on-chip bytes against the guide's aggregate LDS rate) and
-`cpu_baseline` + `parity_sample` (the reference decoder compiled from its sources, oracle/_ref,
-one worker process per host core of this GPU's CPU share, over a bounded
-sample of the same frames).
+Rank 0 prints one JSON line.  A plain run does only what the headline needs:
+set-up, the warm-up and the timed steps, `--dump-outputs DIR` if given, the
+line.  `--full` adds the legs that take runs of their own: `roofline` for the
+decode kernel (a profiled pass of `--steps` more decode calls with HIP events
+around each launch on the launch stream; on-chip bytes against the guide's
+aggregate LDS rate, and the LDS probe kernels), `monte_carlo_e2e` (generate +
+decode + count) and `cpu_baseline` + `parity_sample` (the reference decoder
+compiled from its sources, oracle/_ref, one worker process per host core of
+this GPU's CPU share, over a bounded sample of the same frames).
+`--no-e2e` / `--no-cpu-baseline` drop single legs of a `--full` run.
+
+`--dump-outputs DIR` writes what the last timed step returned, the decoded
+bits of the resident frames, as DIR/decoded_bits.npy (float32 [rows, K]; all
+frames, or a fixed seeded sample of DUMP_ROWS of them in ascending order) and
+the global frame ids of those rows as DIR/frame_ids.npy (float64).  The frames
+are a function of the arguments alone (Philox keyed by global frame id), so
+two builds can be compared output for output.  Rank r > 0 of a multi-GPU run
+writes <name>_rank<r>.npy.
 """
 from __future__ import annotations
 
@@ -52,6 +64,8 @@ GUIDE_LDS_B32_GBS = 75000.0  # MI355X_MICROARCH.md §LDS: aggregate ds_read_b32,
 GUIDE_LDS_B64_GBS = 150000.0  # ... ds_read_b64 / b128
 ONCHIP_BYTES_PER_LOOKUP = 4  # 2 operand symbols + 1 table byte + 1 result byte
 METRIC = "decoded frames/sec (N=1024, SCL-LUT L=8, Q=16) at 1/2/4/8 GPUs; BER match"
+DUMP_ROWS = 1 << 14  # --dump-outputs sample: 2^14 frames x 512 bits x 4 B = 32 MB at the default configuration
+DUMP_SEED = 20240
 KINDS = ["SC-LUT", "SCL-LUT", "FastSC-LUT", "FastSCL-LUT", "CA-SCL-LUT", "CA-FastSCL-LUT"]
 
 
@@ -68,9 +82,14 @@ def parse(argv=None):
                     help="frames per GPU per step (one decode launch: 2^23 x 4 KB int32 symbols = 32 GB resident)")
     ap.add_argument("--ebn0", type=float, default=2.0)
     ap.add_argument("--max-waves", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline pass, the generate+decode+count rate and the "
+                         "CPU baseline with its parity sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the decoded bits of the last timed step (a fixed sample of a large batch) as DIR/*.npy")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the generate+decode+count rate")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity sample")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the generate+decode+count rate")
     ap.add_argument("--engine", default="auto", choices=["auto", "fast", "generic"])
     ap.add_argument("--luts", default="mindistortion", choices=["mindistortion", "minsum"],
                     help="decoder tables: MinDistortion design (lutgen.py) or synthetic saturating min-sum")
@@ -208,12 +227,15 @@ def run_rank(args, ctx, wl):
     import torch.distributed as dist
 
     dec = wl.dec
-    prof = _has_prof(dec) and ctx._cuda
-    if prof:
-        dec.profile(True)
     out, wall = timed_steps(ctx, lambda: dec.decode_batch(wl.sym), args.steps, args.warmup)
-    kt = dec.kernel_times() if prof else {}
-    if prof:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, wl.frame0, ctx.rank)
+    kt = {}
+    if args.full and _has_prof(dec) and ctx._cuda:  # the roofline's kernel times: a profiled pass of its own
+        dec.profile(True)
+        dec.kernel_times()  # reads reset the sums
+        timed_steps(ctx, lambda: dec.decode_batch(wl.sym), args.steps, 0)
+        kt = dec.kernel_times()
         dec.profile(False)
 
     # error counters (BER/BLER) -- the only collectives: RCCL all-reduces
@@ -261,8 +283,28 @@ def run_rank(args, ctx, wl):
                               "ops": info["num_ops"], "prefix_ops": info.get("prefix_ops", 0),
                               "waves": min(info["max_waves"], -(-frames // info["frames_per_wave"]))})
     if kt:
-        res["roofline"] = roofline(args, dec, kt, frames, args.steps + args.warmup)
+        res["roofline"] = roofline(args, dec, kt, frames, args.steps)
     return res
+
+
+def dump_rows(frames, limit=DUMP_ROWS, seed=DUMP_SEED):
+    """Row indices --dump-outputs keeps: every frame up to `limit`, else a fixed
+    seeded sample of `limit` of them, ascending."""
+    if frames <= limit:
+        return np.arange(frames, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(frames, size=limit, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, out, frame0, rank=0):
+    """--dump-outputs: the bits decode_batch returned in the last timed step."""
+    import torch
+
+    rows = dump_rows(int(out.shape[0]))
+    bits = out[torch.from_numpy(rows).to(out.device)].to(torch.float32).cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if rank else ""
+    np.save(os.path.join(path, f"decoded_bits{tag}.npy"), bits)
+    np.save(os.path.join(path, f"frame_ids{tag}.npy"), (rows + frame0).astype(np.float64))
 
 
 def _counters_key(args, frames):
@@ -551,14 +593,15 @@ def cpu_model() -> str:
 
 def rank_job(args, ctx, make_workload):
     """Everything one rank runs: its workload (global frames [r*F, (r+1)*F) of
-    one Philox stream), then the throughput steps and the end-to-end rate, or
-    the Monte-Carlo point.  Returns (rank 0's result dict or None, workload)."""
+    one Philox stream), then the throughput steps and, with --full, the
+    end-to-end rate; or the Monte-Carlo point.  Returns (rank 0's result dict
+    or None, workload)."""
     wl = make_workload(ctx.rank * args.frames, 0 if args.mc_frames else args.frames)
     ctx.sync()
     if args.mc_frames:
         return mc_rank(args, ctx, wl), wl
     res = run_rank(args, ctx, wl)
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         e2e = e2e_rate(args, ctx, wl)
         if res is not None:
             res["monte_carlo_e2e"] = e2e
@@ -611,7 +654,7 @@ def main(argv=None):
                         frame0=frame0, device=dev.index, max_waves=args.max_waves, engine=args.engine)
 
     res, wl = rank_job(args, ctx, make)
-    if not args.mc_frames and not args.no_cpu_baseline:
+    if args.full and not args.mc_frames and not args.no_cpu_baseline:
         if res is not None:
             parity_and_baseline(args, wl, res)
             res["config"]["process_group"] = dist.get_backend(group) if group is not None else None

@@ -103,7 +103,8 @@ def run_world(world, argv):
 @pytest.mark.parametrize("world", [1, 2])
 def test_bench_rank_job_shards_and_reduces(world):
     F, steps = 96, 3
-    out = run_world(world, ["--frames", str(F), "--steps", str(steps), "--warmup", "1", "--N", str(N), "--K", str(K)])
+    out = run_world(world, ["--full", "--frames", str(F), "--steps", str(steps), "--warmup", "1", "--N", str(N),
+                            "--K", str(K)])
     res = out[0][0]
     assert all(out[r][0] is None for r in range(1, world))  # only rank 0 reports
     # rank r decoded global frames [r*F, (r+1)*F): disjoint, covering [0, world*F)
@@ -120,6 +121,63 @@ def test_bench_rank_job_shards_and_reduces(world):
     for r in range(world):
         later = out[r][1][1:]
         assert len(later) == 1 + steps and all(B == F and f0 >= (1 << 40) for f0, B in later)
+
+
+class CountingDecoder(FakeDecoder):
+    def __init__(self):
+        super().__init__()
+        self.calls = 0
+
+    def decode_batch(self, sym):
+        self.calls += 1
+        return super().decode_batch(sym)
+
+
+def _plain_job(argv):
+    import torch
+
+    ranges = []
+    make = fake_make(ranges)
+
+    def counting(frame0, frames):
+        wl = make(frame0, frames)
+        wl.dec = CountingDecoder()
+        return wl
+
+    res, wl = bench.rank_job(bench.parse(argv), bench.Ctx(0, 1, torch.device("cpu")), counting)
+    return res, wl, ranges
+
+
+def test_plain_run_times_its_steps_and_nothing_else():
+    """Without --full: warm-up + exactly --steps decode calls on the resident
+    frames, no end-to-end leg, and the headline fields of the result line."""
+    F, steps, warmup = 64, 4, 2
+    res, wl, ranges = _plain_job(["--frames", str(F), "--steps", str(steps), "--warmup", str(warmup), "--N", str(N),
+                                  "--K", str(K)])
+    assert wl.dec.calls == steps + warmup and ranges == [(0, F)]
+    assert "monte_carlo_e2e" not in res and "roofline" not in res and "cpu_baseline" not in res
+    assert (res["metric"], res["unit"], res["higher_is_better"], res["dtype"]) == (bench.METRIC, "frames/s", True, "u8")
+    assert res["steps"] == steps and res["ms_per_step"] > 0
+    assert res["value"] == pytest.approx(F * steps / (res["ms_per_step"] * steps / 1e3))
+
+
+@pytest.mark.parametrize("F", [48, bench.DUMP_ROWS + 1000])
+def test_dump_outputs_writes_the_last_steps_bits(F, tmp_path):
+    """--dump-outputs: float32 bits of the last timed step, every frame of a
+    small batch or the fixed ascending sample of a large one, with the global
+    frame ids of the rows; the same rows on a second run."""
+    argv = ["--frames", str(F), "--steps", "1", "--warmup", "0", "--N", str(N), "--K", str(K)]
+    for d in ("a", "b"):
+        _plain_job(argv + ["--dump-outputs", str(tmp_path / d)])
+    bits, ids = np.load(tmp_path / "a" / "decoded_bits.npy"), np.load(tmp_path / "a" / "frame_ids.npy")
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["decoded_bits.npy", "frame_ids.npy"]
+    assert bits.dtype == np.float32 and ids.dtype == np.float64
+    assert bits.shape == (min(F, bench.DUMP_ROWS), K) and ids.shape == (len(bits),)
+    assert bits.nbytes + ids.nbytes <= 64 << 20
+    assert np.all(np.diff(ids) > 0) and ids[0] >= 0 and ids[-1] < F
+    assert np.array_equal(bits, frame_bits(0, F)[ids.astype(np.int64), :K].astype(np.float32))
+    assert np.array_equal(bits, np.load(tmp_path / "b" / "decoded_bits.npy"))
+    assert np.array_equal(ids, np.load(tmp_path / "b" / "frame_ids.npy"))
 
 
 @pytest.mark.parametrize("world,stop", [(1, 0), (2, 0), (2, 20)])

@@ -123,7 +123,7 @@ def test_bench_throughput_line_through_rccl(rccl, make):
 
     out = {}
     for name, grp in (("rccl", rccl), ("none", None)):
-        args = _args(["--frames", "16384", "--steps", "2", "--warmup", "1"])
+        args = _args(["--full", "--frames", "16384", "--steps", "2", "--warmup", "1"])
         out[name], wl = bench.rank_job(args, _ctx(grp), make)
     a, b = out["rccl"], out["none"]
     for k in ("ber", "bler", "frames_counted", "n_gpus"):

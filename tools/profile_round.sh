@@ -15,7 +15,7 @@ O=gpurun_out/prof_$TAG
 P=gpurun_out/profiles_$TAG
 mkdir -p "$O" "$P"
 B1="--steps 1 --warmup 0 --no-cpu-baseline --no-e2e $ARGS"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/kt" -o kt --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline $ARGS > "$O/kt.log" 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/kt" -o kt --output-format csv -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline $ARGS > "$O/kt.log" 2>&1
 pass() {  # name counters...
   local name=$1; shift
   timeout -s KILL 240 rocprofv3 --pmc "$@" -d "$O/$name" -o "$name" --output-format csv -- python3 bench.py $B1 > "$O/$name.log" 2>&1
