@@ -88,7 +88,10 @@ enum qpd_kind {
 enum qpd_status {
     QPD_OK = 0,
     QPD_E_INVALID = -1,     /* bad argument / configuration                  */
-    QPD_E_UNSUPPORTED = -2, /* valid for the reference, not supported here   */
+    QPD_E_UNSUPPORTED = -2, /* valid for the reference, not supported here -- or
+                             * not by the engine asked for (QPD_ENGINE_FAST on
+                             * tables, a list size or a plan it does not serve:
+                             * qpd_last_error() says which)                  */
     QPD_E_DEVICE = -3,      /* HIP runtime failure                           */
     QPD_E_INPUT = -4        /* input the reference cannot decode defined-ly,
                                seen on device: a channel symbol outside
@@ -111,7 +114,9 @@ typedef struct qpd_config {
     int32_t kind;               /* enum qpd_kind                                  */
     int32_t N;                  /* code length, power of two, 2..65536            */
     int32_t K;                  /* output bits = number of 0 entries in frozen    */
-    int32_t L;                  /* list size (SCL kinds), 1..32 (> 8: generic engine); ignored otherwise */
+    int32_t L;                  /* list size (SCL kinds), 1..32; ignored otherwise.  Fast engine: L <= 8;
+                                 * SCL-LUT / CA-SCL-LUT also 9..16; FastSCL-LUT / CA-FastSCL-LUT 9..16 only on
+                                 * an explicit QPD_ENGINE_FAST (AUTO: generic engine).  Above: generic engine */
     int32_t v;                  /* symbol alphabet size, 2..256 (LUT kinds); the
                                    re-quantizer's v (uniform kinds: M = (v/2 - 0.5) r_f,
                                    (v/2 - 1) r_g, integer v/2)                    */
@@ -161,7 +166,12 @@ typedef struct qpd_config {
 } qpd_config;
 
 /* Kernel selection.  AUTO picks FAST when the tables allow it (one table per
- * node, v <= 16) and GENERIC otherwise; the env var QPD_ENGINE overrides. */
+ * node, v <= 16) and the list size is at most 8 (SCL-LUT / CA-SCL-LUT: 16), and
+ * GENERIC otherwise; the env var QPD_ENGINE overrides.  FAST asked for
+ * explicitly also serves FastSCL-LUT / CA-FastSCL-LUT with 9 <= L <= 16 (lane
+ * groups of 16) unless the code has an R1 node of more than 32 elements, or of
+ * more than 16 whose argsort finds no room in LDS: then, as for everything else
+ * the fast engine does not serve, qpd_create returns QPD_E_UNSUPPORTED. */
 enum qpd_engine { QPD_ENGINE_AUTO = 0, QPD_ENGINE_GENERIC = 1, QPD_ENGINE_FAST = 2 };
 
 typedef struct qpd_decoder qpd_decoder;

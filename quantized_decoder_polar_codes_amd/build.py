@@ -29,6 +29,7 @@ UNITS = [
     ("qpd_k_scl1.hip", []),
     ("qpd_fast_fscl.hip", []),
     ("qpd_fast_fscl1.hip", []),
+    ("qpd_fast_fscl16.hip", []),
     ("qpd_k_generic.hip", []),
     ("qpd_lutgen.cpp", []),
 ]

@@ -25,6 +25,7 @@ const void *fast_kernel_scl(int sets, bool l8, bool w16);        // qpd_k_scl.hi
 const void *fast_kernel_scl_pw1(int sets, bool l8, bool w16);    // qpd_k_scl1.hip
 const void *fast_kernel_fscl(int sets, bool l8, bool r1l);       // qpd_fast_fscl.hip
 const void *fast_kernel_fscl_pw1(int sets, bool l8, bool r1l);   // qpd_fast_fscl1.hip
+const void *fast_kernel_fscl_w16(int sets, bool pw1);            // qpd_fast_fscl16.hip
 const void *generic_kernel(int fam, int dom, bool wide);         // qpd_k_generic.hip
 }  // namespace qpd
 #include "qpd_mc.hip"
@@ -88,7 +89,7 @@ struct qpd_decoder {
     DeviceBuf mc_pref, mc_crc;  // qpd_mc_frames: info bits before each word; CRC contribution per message bit
     int sets = 1;  // fast engine: frame sets per wave (lut_fast_kernel NS)
     bool l8 = false;  // fast engine: list decoder with L = 8 (select_survivors8)
-    bool w16 = false; // fast engine: SCL-LUT with 9 <= L <= 16 (lane groups of 16, select_survivors16)
+    bool w16 = false; // fast engine: SCL-LUT / FastSCL-LUT with 9 <= L <= 16 (lane groups of 16, select_survivors16)
     bool r1l = false;  // fast engine: an R1 node needs r1_large (the R1L instantiation)
     bool pw1 = false;  // fast engine: one pointer word per path (compact_pointer_fields)
     bool pre = false;         // fast engine pre-mode: root_pre_kernel, then the decode on its rows
@@ -1018,7 +1019,9 @@ const void *fast_kernel(int kind, int sets, bool l8, bool r1l, bool pw1, bool w1
         case QPD_SC_LUT:
         case QPD_FASTSC_LUT: return pw1 || r1l ? nullptr : qpd::fast_kernel_single(kind, sets);
         case QPD_SCL_LUT: return r1l ? nullptr : pw1 ? qpd::fast_kernel_scl_pw1(sets, l8, w16) : qpd::fast_kernel_scl(sets, l8, w16);
-        case QPD_FASTSCL_LUT: return w16 ? nullptr : pw1 ? qpd::fast_kernel_fscl_pw1(sets, l8, r1l) : qpd::fast_kernel_fscl(sets, l8, r1l);
+        case QPD_FASTSCL_LUT:
+            if (w16) return r1l ? nullptr : qpd::fast_kernel_fscl_w16(sets, pw1);
+            return pw1 ? qpd::fast_kernel_fscl_pw1(sets, l8, r1l) : qpd::fast_kernel_fscl(sets, l8, r1l);
         default: return nullptr;
     }
 }
@@ -1196,7 +1199,11 @@ int build_fast(qpd_decoder *d, const qpd_config *c, const Schedule &s) {
     if (const char *e = getenv("QPD_SETS")) if (atoi(e) == 3 && c->kind == QPD_SCL_LUT && d->L == 8) d->sets = 3;
 #endif
     d->l8 = (c->kind == QPD_SCL_LUT || c->kind == QPD_FASTSCL_LUT) && d->L == 8;
-    d->w16 = c->kind == QPD_SCL_LUT && d->L > qpd::kMaxL;
+    // lane groups of 16: SCL-LUT, and FastSCL-LUT where the fast engine was asked for (qpd_create:
+    // AUTO keeps it on the generic engine).  FastSCL-LUT's W16 plan has no mixed bottom subtrees
+    // and no folded special nodes (Ly.botx below: both are L = 8 code), its special nodes run
+    // through the single-set special_op, one frame set after the other.
+    d->w16 = (c->kind == QPD_SCL_LUT || c->kind == QPD_FASTSCL_LUT) && d->L > qpd::kMaxL;
     const int NS = d->sets;
     FastLayout Ly;
     Ly.ns = NS;
@@ -1354,7 +1361,7 @@ int build_fast(qpd_decoder *d, const qpd_config *c, const Schedule &s) {
     place_syncs(pp.st2, true);
     place_syncs(mops, c->kind == QPD_SCL_LUT || c->kind == QPD_FASTSCL_LUT);
     // one pointer word: the list kinds at one or two frame sets (the instantiations
-    // fast_kernel() has); FastSCL-LUT only at two sets with L = 8 and no r1_large
+    // fast_kernel() has); FastSCL-LUT only at two sets with L = 8 and no r1_large, or W16
     // Special nodes the lean code of the R1L = false kernels cannot take: R1 nodes of > 16
     // elements without their LDS tail (r1_large), or (L = 8) R1 nodes without ranks in the
     // op record and R0 / REP nodes without one quanta row
@@ -1364,8 +1371,13 @@ int build_fast(qpd_decoder *d, const qpd_config *c, const Schedule &s) {
               ((m.cnt > qpd::stl::kThreshold && !(m.flags & qpd::MF_R1_LDS)) || (d->l8 && !(m.flags & qpd::MF_R1_RK)))) ||
              (d->l8 && (m.type == qpd::OP_R0 || m.type == qpd::OP_REP) && !(m.flags & qpd::MF_VUNI))))
             d->r1l = true;
+    // the W16 FastSCL-LUT kernels have no r1_large: such a plan is not served (the generic engine decodes it)
+    if (c->kind == QPD_FASTSCL_LUT && d->w16 && d->r1l)
+        return fail(QPD_E_UNSUPPORTED,
+                    "fast engine, FastSCL-LUT with L > 8: an R1 node of more than 32 elements, or of more than 16 "
+                    "without room for its argsort in LDS, is not served (use the generic engine)");
     // (SCL-LUT only with the root pre-pass: those kernels have no channel reads, lut_fast_kernel kChan)
-    const bool pw1_ok = c->kind == QPD_SCL_LUT ? NS <= 2 && Ly.pre : (c->kind == QPD_FASTSCL_LUT && NS == 2 && d->l8 && !d->r1l);
+    const bool pw1_ok = c->kind == QPD_SCL_LUT ? NS <= 2 && Ly.pre : (c->kind == QPD_FASTSCL_LUT && ((NS == 2 && d->l8 && !d->r1l) || d->w16));
     if (pw1_ok && !getenv("QPD_NO_PW1")) d->pw1 = compact_pointer_fields({&mops, &pp.st1, &pp.st1b, &pp.st2});
     d->pfx_nops = (int)pp.st1.size();
     d->pfx1b_nops = (int)pp.st1b.size();
@@ -1570,19 +1582,22 @@ int qpd_create(const qpd_config *cfg, qpd_decoder **out) {
     visit(s, c->kind, c->N, n, c->frozen_bits, (c->kind == QPD_FASTSC_LUT || c->kind == QPD_FASTSCL_LUT) ? c->node_type : nullptr, 0, 0);
     d->ops_host = s.ops;
     {
-        // L > 8 (2L > 16: libstdc++ introsort, replayed where ties make it matter): SCL-LUT up to
-        // L = 16 on the fast engine (lane groups of 16, select_survivors16), the others on the generic one
-        const bool fast_ok = dom == qpd::DOM_LUT && c->f_step == 0 && c->g_step == 0 && c->v <= 16 &&
-                             (d->L <= qpd::kMaxL || (c->kind == QPD_SCL_LUT && d->L <= 2 * qpd::kMaxL));
+        // L > 8 (2L > 16: libstdc++ introsort, replayed where ties make it matter): up to L = 16 on
+        // the fast engine (lane groups of 16, select_survivors16) -- SCL-LUT under AUTO, FastSCL-LUT
+        // only on an explicit request (fast_avail): AUTO keeps it on the generic engine
+        const bool fast_base = dom == qpd::DOM_LUT && c->f_step == 0 && c->g_step == 0 && c->v <= 16;
+        const bool fast_auto = fast_base && (d->L <= qpd::kMaxL || (c->kind == QPD_SCL_LUT && d->L <= 2 * qpd::kMaxL));
+        const bool fast_avail = fast_auto || (fast_base && c->kind == QPD_FASTSCL_LUT && d->L <= 2 * qpd::kMaxL);
         int want = c->engine;
         if (const char *e = getenv("QPD_ENGINE")) want = atoi(e);
-        if (want == QPD_ENGINE_FAST && !fast_ok) {
+        if (want == QPD_ENGINE_FAST && !fast_avail) {
             delete d;
             return fail(QPD_E_UNSUPPORTED,
                         "fast engine needs LUT symbols with one table per node (f_step = g_step = 0), v <= 16 and L <= 8 "
-                        "(SCL-LUT: L <= 16)");
+                        "(SCL-LUT and, on request, FastSCL-LUT: L <= 16)");
         }
-        d->engine = (want == QPD_ENGINE_GENERIC || !fast_ok) ? QPD_ENGINE_GENERIC : QPD_ENGINE_FAST;
+        d->engine = want == QPD_ENGINE_FAST ? QPD_ENGINE_FAST
+                    : (want == QPD_ENGINE_GENERIC || !fast_auto) ? QPD_ENGINE_GENERIC : QPD_ENGINE_FAST;
     }
 
     DevPlan &P = d->plan;

@@ -1121,6 +1121,28 @@ __device__ __forceinline__ Sel select_survivors16(double kk, double kf, int gl, 
     return s;
 }
 
+// The one selection entry point of the list decoders' forks: keep key kk and
+// flip key kf of this lane's path -> its slot's surviving candidate (parent,
+// upper), as mink does on [keeps | flips] (SCLLUTDecoder.cpp:105-144 and
+// FastSCLLUTDecoder.cpp:129, 187, 256, 332: every call site lays its 2L keys
+// out as keep i at i, flip i at L + i, dead paths' +inf entries included).
+// LM = 8: groups of 8 (DPP ranks), 16: L = 9..16 (the introsort replay), else
+// the generic stable ranks of L <= 8.  fork_identity: the selection is known
+// to be the identity in every group of the wave (never for the generic form).
+template <int LM>
+__device__ __forceinline__ bool fork_identity(double kk, double kf, int gl, int gbase, int L) {
+    if constexpr (LM == 8) return keep_all8(__builtin_bit_cast(uint64_t, kk), __builtin_bit_cast(uint64_t, kf), gl);
+    else if constexpr (LM == 16)
+        return keep_all16(__builtin_bit_cast(uint64_t, kk), __builtin_bit_cast(uint64_t, kf), gl, gbase, L);
+    else return false;
+}
+template <int LM>
+__device__ __forceinline__ Sel fork_select(double kk, double kf, int gl, int gbase, int L, int lane, int *sel, int sj) {
+    if constexpr (LM == 8) return select_survivors8(kk, kf, gl, gbase, lane, sel, sj);
+    else if constexpr (LM == 16) return select_survivors16(kk, kf, gl, gbase, L, lane, sel, sj);
+    else return select_survivors(kk, kf, gl, gbase, L, sel);
+}
+
 // Info leaf with quanta dm: keep the L best of {keep, flip} candidates.
 // Returns the new decision; `extra` words follow the surviving lineage.
 // `moved` (wave-uniform): the selection was not the identity (paths moved).
@@ -1134,14 +1156,9 @@ __device__ __forceinline__ uint32_t leaf_fork(Path &st, double dm, int gl, int g
     // Fast path (about 2/3 of the info leaves on the bench channel): the
     // selection is the identity, the decision the hard one.
     moved = false;
-    if constexpr (LM == 8)
-        if (keep_all8(__builtin_bit_cast(uint64_t, st.pm), __builtin_bit_cast(uint64_t, kf), gl)) return hd;
-    if constexpr (LM == 16)
-        if (keep_all16(__builtin_bit_cast(uint64_t, st.pm), __builtin_bit_cast(uint64_t, kf), gl, gbase, L)) return hd;
+    if (fork_identity<LM>(st.pm, kf, gl, gbase, L)) return hd;
     moved = true;
-    const Sel sl = LM == 8    ? select_survivors8(st.pm, kf, gl, gbase, lane, sel, sj)
-                   : LM == 16 ? select_survivors16(st.pm, kf, gl, gbase, L, lane, sel, sj)
-                              : select_survivors(st.pm, kf, gl, gbase, L, sel);
+    const Sel sl = fork_select<LM>(st.pm, kf, gl, gbase, L, lane, sel, sj);
     const int p = gbase + sl.parent;
     const uint32_t dec = (uint32_t)lane_read((int)hd, p) ^ (sl.upper ? 1u : 0u);
     st.pm = pick(sl.upper, shfld(kf, p), shfld(st.pm, p));
@@ -1796,19 +1813,59 @@ struct LdsSeq16 {
     __device__ __forceinline__ bool less(int a, int b) const { return (a >> 5) < (b >> 5); }  // keys only, as std::sort
 };
 
+// The argsort half of an R1 node of <= 32 elements (:100-116) for one set:
+// the m smallest |l| in std::sort's order, packed for r1_layers -- ord[q] =
+// element of the q-th smallest |llr| (5 bits each) and its symbol (4 bits
+// each), hw = hard decisions (l < 0).  MAXM bounds the layers m = min(L - 1,
+// temp): kMaxM = 7 (L <= 8: ordp0 holds 6 entries, ordp1 the seventh, symp all
+// symbols) or 15 (L = 9..16: three order words of 6 entries, two symbol words of 8).
+template <int MAXM>
+struct R1PrepT;
+template <>
+struct R1PrepT<kMaxM> {
+    uint32_t ordp0, ordp1, symp, hw;
+    __device__ __forceinline__ int ord(int layer) const {
+        return (int)(layer < 6 ? __builtin_amdgcn_ubfe(ordp0, 5 * layer, 5) : ordp1);
+    }
+    __device__ __forceinline__ uint32_t sym(int layer) const { return __builtin_amdgcn_ubfe(symp, 4 * layer, 4); }
+    __device__ __forceinline__ void put(int q, int o, uint32_t sy) {
+        symp |= sy << (4 * q);
+        if (q < 6)
+            ordp0 |= (uint32_t)o << (5 * q);
+        else
+            ordp1 = (uint32_t)o;
+    }
+};
+template <>
+struct R1PrepT<15> {
+    uint32_t ordp0, ordp1, ordp2, symp0, symp1, hw;
+    __device__ __forceinline__ int ord(int layer) const {
+        const uint32_t w = layer < 6 ? ordp0 : layer < 12 ? ordp1 : ordp2;
+        const int k = layer < 6 ? layer : layer < 12 ? layer - 6 : layer - 12;
+        return (int)__builtin_amdgcn_ubfe(w, 5 * k, 5);
+    }
+    __device__ __forceinline__ uint32_t sym(int layer) const {
+        return __builtin_amdgcn_ubfe(layer < 8 ? symp0 : symp1, 4 * (layer & 7), 4);
+    }
+    __device__ __forceinline__ void put(int q, int o, uint32_t sy) {  // q: a constant after unrolling
+        (q < 8 ? symp0 : symp1) |= sy << (4 * (q & 7));
+        (q < 6 ? ordp0 : q < 12 ? ordp1 : ordp2) |= (uint32_t)o << (5 * (q % 6));
+    }
+};
+typedef R1PrepT<kMaxM> R1Prep;
+
 // Survivor layers of an R1 node (FastSCLLUTDecoder.cpp:118-166) after its
-// argsort: ord[q] = element of the q-th smallest |llr| (5 bits each in
-// ordp0 / ordp1) and its symbol (4 bits each in symp), hw = hard decisions
-// (l < 0).  Each of the m layers forks on flipping the next element; the flip
+// argsort (R1PrepT).  Each of the m layers forks on flipping the next element; the flip
 // position is the slot's own pre-selection ord (H2).  The arrays never move: a
 // slot's lineage holds the arrays its `origin` lane computed (read per layer
 // by shuffles; each lane re-derives its own entry's magnitude, a quanta-row
 // lookup or a vcl read), and its flips are one bit mask (temp <= 32) shuffled
 // with the survivors.  Returns the node's bits.
-template <bool L8, class Path>
+template <int LM, int MAXM, class Path>
 __device__ __forceinline__ uint32_t r1_layers(Path &st, int *sel, int sj, int gl, int gbase, int lane, int L, int m,
-                                                     uint32_t ordp0, uint32_t ordp1, uint32_t symp, bool uni,
-                                                     double vrow, const double *vq, int v, uint32_t hw, int temp) {
+                                                     const R1PrepT<MAXM> &r, bool uni, double vrow, const double *vq, int v,
+                                                     int temp) {
+    const uint32_t hw = r.hw;
     uint32_t flips = 0;
     int origin = gl;
 #if QPD_R1_UNROLL
@@ -1816,23 +1873,26 @@ __device__ __forceinline__ uint32_t r1_layers(Path &st, int *sel, int sj, int gl
 #else
 #pragma unroll 1  // (one copy of the fork code)
 #endif
-    for (int layer = 0; layer < kMaxM; ++layer) {
+    for (int layer = 0; layer < MAXM; ++layer) {
         if (layer < m) {
             const int o = gbase + origin;
-            const int own = (int)(layer < 6 ? __builtin_amdgcn_ubfe(ordp0, 5 * layer, 5) : ordp1);
-            const uint32_t sym = __builtin_amdgcn_ubfe(symp, 4 * layer, 4);
+            const int own = r.ord(layer);
+            const uint32_t sym = r.sym(layer);
             const double own_ms = fabs(uni ? shfld(vrow, (int)sym) : vq[(size_t)own * v + sym]);
             const double kf = st.pm + shfld(own_ms, o);
             // Identity selection in every group: no flip survives and no
             // lineage moves, and since each slot's magnitudes ascend with the
             // layer (argsort order) and pm + a is monotone in a, every later
             // layer's flips are at least as large -- all remaining layers are
-            // the identity too, so the node is decided.
-            if constexpr (L8)
-                if (keep_all8(__builtin_bit_cast(uint64_t, st.pm), __builtin_bit_cast(uint64_t, kf), gl)) break;
+            // the identity too, so the node is decided.  The same holds for the
+            // STRICT identity of L = 9..16 (keep_all16: keeps strictly increasing,
+            // every flip strictly above the largest keep): an identity layer leaves
+            // the keeps as they are, and each slot's flip magnitudes are
+            // non-decreasing with the layer, so flips strictly above the largest
+            // keep stay strictly above it.
+            if (fork_identity<LM>(st.pm, kf, gl, gbase, L)) break;
             const int pos_old = lane_read(own, o);  // H2
-            const Sel sl = L8 ? select_survivors8(st.pm, kf, gl, gbase, lane, sel, sj)
-                              : select_survivors(st.pm, kf, gl, gbase, L, sel);
+            const Sel sl = fork_select<LM>(st.pm, kf, gl, gbase, L, lane, sel, sj);
             const int p = gbase + sl.parent;
             st.pm = pick(sl.upper, shfld(kf, p), shfld(st.pm, p));
             st.move(p);
@@ -1869,17 +1929,14 @@ __device__ __forceinline__ void spec_out(const Mem &M, const MOp &op, Path &st, 
     M.st(op.flags & MF_DST_LDS, op.dst_row + w, lane, res);
 }
 
-// The argsort half of an R1 node of <= 32 elements (:100-116) for one set:
-// the m smallest |l| in std::sort's order, packed for r1_layers.
-struct R1Prep {
-    uint32_t ordp0, ordp1, symp, hw;
-};
-
 // GEN = false (the FastSCL-LUT kernels without R1L): every R1 node has its ranks in
 // the op record (MF_R1_RK, one quanta row) -- the host takes the R1L instantiation
 // otherwise -- so the rank-table and std::sort paths are not compiled.
-template <bool LT = false, bool GEN = true, class Path>
-__device__ __forceinline__ R1Prep r1_prep(const FastPlan &P, const Mem &M, const MOp &op, Path st, int gbase, int L,
+// MAXM: the layer bound (R1PrepT); both argsort paths deliver the first m <= MAXM outputs of
+// std::sort -- <= 16 elements: its insertion sort is stable, the min-tree pick on (rank, element);
+// 17..32: the partitions replayed in the LDS tail, then the m smallest (rank, position) of [0, end).
+template <bool LT = false, bool GEN = true, int MAXM = kMaxM, class Path>
+__device__ __forceinline__ R1PrepT<MAXM> r1_prep(const FastPlan &P, const Mem &M, const MOp &op, Path st, int gbase, int L,
                                           int lane, int temp, uint32_t *lds_wave, uint32_t T2 = 0u,
                                           const uint8_t *tb = nullptr) {
     const int src = gbase + pfield(st.ps, op.sh_src);
@@ -1903,9 +1960,9 @@ __device__ __forceinline__ R1Prep r1_prep(const FastPlan &P, const Mem &M, const
 #pragma unroll
     for (int w = 0; w < 4; ++w)
         W[w] = (8 * w < temp) ? spec_in<LT>(M, op, src, gbase + pfield(st.U(), op.sh_u), w, T2, tb) : 0u;
-    int ord[kMaxM];
+    int ord[MAXM];
 #pragma unroll
-    for (int q = 0; q < kMaxM; ++q) ord[q] = 0;
+    for (int q = 0; q < MAXM; ++q) ord[q] = 0;
     if ((QPD_EXP_FSCL & 8) || temp <= stl::kThreshold) {
         // entries rank << 5 | j (< 2^14) two per register; the m smallest by
         // packed 16-bit min trees (v_pk_min_u16), the taken one set to 0xFFFF
@@ -1927,7 +1984,7 @@ __device__ __forceinline__ R1Prep r1_prep(const FastPlan &P, const Mem &M, const
             ep[i] = __builtin_bit_cast(u16x2, lo | (hi << 16));
         }
 #pragma unroll
-        for (int q = 0; q < kMaxM; ++q) {
+        for (int q = 0; q < MAXM; ++q) {
             if (q < m) {
                 u16x2 a = __builtin_elementwise_min(__builtin_elementwise_min(ep[0], ep[1]),
                                                     __builtin_elementwise_min(ep[2], ep[3]));
@@ -1975,7 +2032,7 @@ __device__ __forceinline__ R1Prep r1_prep(const FastPlan &P, const Mem &M, const
                 ep[i] = __builtin_bit_cast(u16x2, lo | (hi << 16));
             }
 #pragma unroll
-            for (int q = 0; q < kMaxM; ++q) {
+            for (int q = 0; q < MAXM; ++q) {
                 if (q < m) {
                     u16x2 a[8];
 #pragma unroll
@@ -1998,27 +2055,24 @@ __device__ __forceinline__ R1Prep r1_prep(const FastPlan &P, const Mem &M, const
         } else if constexpr (GEN) {
             stl::sort_small_prefix(seq, 0, temp, m);  // only ord[0, m) is read
 #pragma unroll
-            for (int q = 0; q < kMaxM; ++q)
+            for (int q = 0; q < MAXM; ++q)
                 if (q < m) ord[q] = seq.get(q) & 31;
         }
     }
-    R1Prep r{0u, 0u, 0u, hw};
+    R1PrepT<MAXM> r{};
+    r.hw = hw;
 #pragma unroll
-    for (int q = 0; q < kMaxM; ++q) {
+    for (int q = 0; q < MAXM; ++q) {
         if (q < m) {
             const int k = ord[q] >> 3;
             const uint32_t w = k == 0 ? W[0] : k == 1 ? W[1] : k == 2 ? W[2] : W[3];
-            r.symp |= ((w >> (4 * (ord[q] & 7))) & 15u) << (4 * q);
-            if (q < 6)
-                r.ordp0 |= (uint32_t)ord[q] << (5 * q);
-            else
-                r.ordp1 = (uint32_t)ord[q];
+            r.put(q, ord[q], (w >> (4 * (ord[q] & 7))) & 15u);
         }
     }
     return r;
 }
 
-template <bool L8, class Path>
+template <int LM, class Path>
 __device__ __forceinline__ void r1_small(const FastPlan &P, const Mem &M, const MOp &op, Path &st, int *sel, int sj,
                                          int gl, int gbase, int L, int lane, int temp, uint32_t *lds_wave) {
     const int v = P.v;
@@ -2026,9 +2080,11 @@ __device__ __forceinline__ void r1_small(const FastPlan &P, const Mem &M, const 
     const double *vq = P.vcl + (size_t)op.vrow * v;
     const bool uni = op.flags & MF_VUNI;
     const double vrow = uni && (lane & 15) < v ? vq[lane & 15] : 0.0;
-    const R1Prep r = r1_prep(P, M, op, st, gbase, L, lane, temp, lds_wave);
-    const uint32_t word =
-        r1_layers<L8>(st, sel, sj, gl, gbase, lane, L, m, r.ordp0, r.ordp1, r.symp, uni, vrow, vq, v, r.hw, temp);
+    constexpr int MAXM = LM == 16 ? 15 : kMaxM;
+    // (LM = 16: the argsort is done with the LDS tail -- order, symbols and hard decisions are in
+    // registers -- before the first layer's selection writes the scratch inside it)
+    const R1PrepT<MAXM> r = r1_prep<false, true, MAXM>(P, M, op, st, gbase, L, lane, temp, lds_wave);
+    const uint32_t word = r1_layers<LM, MAXM>(st, sel, sj, gl, gbase, lane, L, m, r, uni, vrow, vq, v, temp);
     M.st(op.flags & MF_DST_LDS, op.dst_row, lane, word);
 }
 
@@ -2254,7 +2310,7 @@ __device__ __forceinline__ void r1_large(const FastPlan &P, const Mem &M, const 
 // without LDS room; N >= 2048 codes).  Only those plans get it compiled in:
 // its argsort stack and arrays cost the other instantiations registers and
 // scratch (+3 % FastSCL-LUT at N = 1024 without it).
-template <bool kList, bool L8, bool R1L, class Path>
+template <bool kList, int LM, bool R1L, class Path>
 __device__ __forceinline__ void special_op(const FastPlan &P, const Mem &M, const MOp &op, Path &st, int *sel, int sj,
                                            int gl, int gbase, int L, int lane, uint32_t *lds_wave) {
     const int fl = op.flags;
@@ -2319,10 +2375,10 @@ __device__ __forceinline__ void special_op(const FastPlan &P, const Mem &M, cons
                         kf += l[i] >= 0 ? fabs(l[i]) : 0.0;
                     }
             }
-            if (L8 && keep_all8(__builtin_bit_cast(uint64_t, kk), __builtin_bit_cast(uint64_t, kf), gl)) {
+            if (fork_identity<LM>(kk, kf, gl, gbase, L)) {
                 st.pm = kk;  // identity selection: every path keeps its all-zeros codeword
             } else {
-                const Sel sx = L8 ? select_survivors8(kk, kf, gl, gbase, lane, sel, sj) : select_survivors(kk, kf, gl, gbase, L, sel);
+                const Sel sx = fork_select<LM>(kk, kf, gl, gbase, L, lane, sel, sj);
                 const int p = gbase + sx.parent;
                 st.pm = pick(sx.upper, shfld(kf, p), shfld(kk, p));
                 st.move(p);
@@ -2378,7 +2434,7 @@ __device__ __forceinline__ void special_op(const FastPlan &P, const Mem &M, cons
         }
     } else if (QPD_EXP_FSCL & 4) {
     } else if (temp <= stl::kThreshold || (fl & MF_R1_LDS)) {
-        r1_small<L8>(P, M, op, st, sel, sj, gl, gbase, L, lane, temp, lds_wave);
+        r1_small<LM>(P, M, op, st, sel, sj, gl, gbase, L, lane, temp, lds_wave);
     } else if constexpr (R1L) {
         r1_large(P, M, op, st, sel, gl, gbase, L, lane, temp);
     }
@@ -2431,8 +2487,9 @@ __device__ __forceinline__ void special_op(const FastPlan &P, const Mem &M, cons
 #define QPD_WPE_W16 4  // SCL-LUT at 9 <= L <= 16 (W16): with the all-at-once swaps 5.27 M frames/s at L = 16
                        // vs 5.09 for one swap per round at 4 or 5 waves (r06o; the swaps at 5: 4.52, spills)
 #endif
-// NS frame sets per wave (see above); L8: list decoders with L = 8; W16: SCL-LUT with
-// 9 <= L <= 16 (lane groups of 16, select_survivors16).
+// NS frame sets per wave (see above); L8: list decoders with L = 8; W16: SCL-LUT and
+// FastSCL-LUT with 9 <= L <= 16 (lane groups of 16, select_survivors16; FastSCL-LUT's
+// special nodes through the single-set special_op, R1 nodes with up to 15 layers).
 // LDS: NS * (lds_rows + 2) rows, set-interleaved (see Mem): a set's rows
 // 0..lds_rows-1 (grouped by depth, see FastLayout), then its selection scratch
 // as rows lds_rows (64 slots) and lds_rows + 1 (junk slots).
@@ -2454,7 +2511,8 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
                                                                uint8_t *__restrict__ out,
                                                                const MOp *__restrict__ ops) {
     constexpr bool kList = (KIND == K_SCL_LUT || KIND == K_FASTSCL_LUT);
-    static_assert(!W16 || (KIND == K_SCL_LUT && !L8), "W16: SCL-LUT list sizes 9..16");
+    static_assert(!W16 || (!L8 && (KIND == K_SCL_LUT || (KIND == K_FASTSCL_LUT && !R1L && !PFX))),
+                  "W16: SCL-LUT / FastSCL-LUT list sizes 9..16");
     constexpr int LM = L8 ? 8 : W16 ? 16 : 0;  // list mode of the leaf forks (leaf_fork)
     // staged BOT3 loads: the list kinds (SCL-LUT, FastSCL-LUT)
     constexpr bool kLazy = QPD_BOT3_LAZY && kList;
@@ -2589,14 +2647,14 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
 #if QPD_SPEC_ROT
 #pragma unroll 1
                   for (int s = 0; s < NS; ++s) {
-                    special_op<kList, L8, R1L>(P, Mv[0].set(s), op, stv[0], sel_all + sstride * s, NS * sstride, gl, gbase,
+                    special_op<kList, LM, R1L>(P, Mv[0].set(s), op, stv[0], sel_all + sstride * s, NS * sstride, gl, gbase,
                                                L, lane, lds_rows);
                     rotate_sets(stv);
                   }
 #else
 #pragma unroll
                   for (int s = 0; s < NS; ++s)
-                    special_op<kList, L8, R1L>(P, Mv[s], op, stv[s], sel_all + sstride * s, NS * sstride, gl, gbase, L, lane,
+                    special_op<kList, LM, R1L>(P, Mv[s], op, stv[s], sel_all + sstride * s, NS * sstride, gl, gbase, L, lane,
                                                lds_rows);
 #endif
               }

@@ -1,7 +1,7 @@
 // qpd_k_fast.hip -- decode kernel instantiations (lut_fast_kernel, qpd_fast.hip)
 // of SC-LUT and FastSC-LUT, and the frozen-prefix stages' (lut_prefix_kernel).
 // The instantiations are spread over several translation units (this one,
-// qpd_k_scl.hip, qpd_k_scl1.hip, qpd_fast_fscl.hip, qpd_fast_fscl1.hip; build.py
+// qpd_k_scl.hip, qpd_k_scl1.hip, qpd_fast_fscl.hip, qpd_fast_fscl1.hip, qpd_fast_fscl16.hip; build.py
 // UNITS) that compile in parallel.  nullptr for a combination that has no
 // instantiation, so the launch fails loudly.
 #define QPD_FAST_TEMPLATES_ONLY
