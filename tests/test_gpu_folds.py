@@ -1,4 +1,4 @@
-"""Folded ops of the SCL-LUT schedule (qpd_capi.hip: fuse_descent, fold_combine;
+"""Folded ops of the SCL-LUT schedule (qpd_plan.hpp: fuse_descent, fold_combine;
 qpd_fast.hip: ff_op, the MF_BC2 end of bot3_op).  An F / G op that also runs
 its left child's f from registers, and a right BOT3 that also runs its
 grandparent's combine, must give the bits of the unfolded schedule
