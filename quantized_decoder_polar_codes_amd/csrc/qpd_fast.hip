@@ -906,8 +906,13 @@ __device__ __forceinline__ void rank16_packed(uint32_t X, LessM &lessm, V &acc) 
     }
 }
 
+// kDiag (the selection harness of tests/native/sel_harness.hip only): the lane groups
+// whose bit (gbase / 16) is set in `serial_groups` take the serial replay from the
+// start, beside groups that run the parallel one.  The decode kernels use the default:
+// the mask is not read and the branch compiles out.
+template <bool kDiag = false>
 __device__ __forceinline__ Sel select_survivors16(double kk, double kf, int gl, int gbase, int L, int lane, int *sel,
-                                                  int sj) {
+                                                  int sj, uint32_t serial_groups = 0) {
     const uint64_t kInfBits = 0x7ff0000000000000ull;
     const bool pad = gl >= L;
     const uint64_t K = pad ? kInfBits : __builtin_bit_cast(uint64_t, kk);
@@ -921,6 +926,10 @@ __device__ __forceinline__ Sel select_survivors16(double kk, double kf, int gl, 
     const int n2 = 2 * L;
     int f = 0, l = n2, dl = 2 * stl::lg(n2), end = n2;
     bool live = true, serial = false;
+    if constexpr (kDiag) {
+        serial = (serial_groups >> (gbase >> 4)) & 1u;
+        live = !serial;
+    }
 #pragma unroll 1
     while (__builtin_amdgcn_ballot_w64(live)) {
         if (live && dl == 0) {  // heap-sort fallback: the group replays serially below

@@ -11,7 +11,9 @@ must give the reference's bits:
   MinDistortion bench tables on AWGN frames, L = 9 / 12 / 16;
 * against the generic engine (pinned by the L = 12 / 16 reference goldens) on
   2^14 bench frames at L = 16;
-* noiseless codewords at N = 1024, L = 16 decode to their messages (2^16 frames).
+* noiseless codewords at N = 1024, L = 16 decode to their messages (2^16 frames);
+* one oracle case under the schedule switches (one / two frame sets, two pointer
+  words per path, no frozen-prefix stage).
 """
 import dataclasses
 
@@ -114,3 +116,38 @@ def test_w16_noiseless_roundtrip(qpd):
     assert d.info()["engine"] == 2
     got = d.decode_batch(torch.from_numpy(sym).cuda()).cpu().numpy()
     assert np.array_equal(got, msg)
+
+
+_SWITCHES = ("QPD_SETS", "QPD_NO_PW1", "QPD_NO_PFX")
+
+
+@pytest.mark.parametrize("env,fpw", [({"QPD_SETS": "1"}, 4), ({"QPD_SETS": "2"}, 8), ({"QPD_NO_PW1": "1"}, 8),
+                                     ({"QPD_NO_PFX": "1"}, 8)], ids=["sets1", "sets2", "no_pw1", "no_pfx"])
+def test_w16_schedule_switches(env, fpw, qpd, oracle_mod, monkeypatch):
+    """The W16 instantiations the default plan does not pick -- one frame set
+    (lut_fast_kernel<K_SCL_LUT, 1, ..., W16>), two pointer words per path, the
+    schedule without its frozen-prefix stage -- decode the oracle's bits on
+    tie-heavy tables."""
+    from quantized_decoder_polar_codes_amd import lut as LU
+
+    N, K, L = 256, 128, 16
+    p = LU.random_luts(N, 16, seed=N + L, distinct_mags=3)
+    fm, nt = _code(N, K)
+    rng = np.random.default_rng(N * L)
+    sym = rng.integers(0, 16, size=(160, N), dtype=np.int32)
+    sym[:40] = np.clip(sym[:40] // 2 + 8, 0, 15)
+    sym[40:80] = 7
+    for k in _SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    dec = qpd.from_packed("SCL-LUT", p, K, fm, L=L, engine="fast")
+    info = dec.info()
+    assert info["engine"] == 2 and info["lanes_per_frame"] == 16, info
+    assert info["frames_per_wave"] == fpw
+    if "QPD_NO_PW1" in env:
+        assert info["fast_variant"] & 1 == 0
+    if "QPD_NO_PFX" in env:
+        assert info["prefix_ops"] == 0
+    want = oracle_mod.decode_lut("SCL-LUT", p, K, L, fm, sym, node_type=nt)
+    assert_frames_equal(dec.decode_batch(sym), want, dec, f"w16-switch-{env}")
