@@ -33,7 +33,7 @@ UNITS = [
     ("qpd_k_generic.hip", []),
     ("qpd_lutgen.cpp", []),
 ]
-COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
+COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Werror=undef"]
 
 
 def source_hash() -> str:

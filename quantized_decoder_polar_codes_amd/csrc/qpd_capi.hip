@@ -15,7 +15,8 @@
 
 #include "qpd.h"
 #include "qpd_generic.hip"
-#include "qpd_fast.hip"
+#include "qpd_fast_plan.hpp"
+#include "qpd_fast_pre.hpp"
 
 // Kernel instantiations, each in its own translation unit (build.py UNITS:
 // the units compile in parallel).
@@ -106,18 +107,21 @@ struct qpd_decoder {
     qpd::FastPlan fplan{};
     DeviceBuf f_tab, g_tab, fscratch, mops, r1_rank, task_ctr;
     int num_mops = 0;
-    DeviceBuf pfx_mops;  // frozen-prefix stages' ops (lut_prefix_kernel): stage 1, then stage 2
-    int pfx_nops = 0;    // stage 1 (one path per frame); 0: no split
-    int pfx1b_nops = 0;  // stage 1b (<= 2 live paths); 0: stage 2 resumes from stage 1
-    int pfx2_nops = 0;   // stage 2 (<= 4 live paths); 0: the decode kernel resumes from stage 1
+    DeviceBuf pfx_mops;  // frozen-prefix stages' ops (lut_prefix_kernel): stage 1, stage 1b, then stage 2
     int pfx_sets = 1;    // frame sets per wave of the prefix stages (QPD_PFX_SETS)
-    int pfx1_rec = 0, pfx1_pm = 0;  // stage 1: words per record, metric word in it
-    int pfx1b_rec = 0, pfx1b_pm = 0;  // stage 1b: words per path record, metric word in it
-    int pfx2_rec = 0, pfx2_pm = 0;    // stage 2: words per path record, metric word in it
-    DeviceBuf pfx1_buf, pfx1b_buf, pfx2_buf;  // the stages' records (interleaved, see FastPlan::pfx)
-    size_t pfx1_cap = 0, pfx1b_cap = 0, pfx2_cap = 0;
+    // The stages in FastHostPlan's order: 1 (one path per frame; no ops: no split), 1b (<= 2 live
+    // paths; no ops: stage 2 resumes from stage 1), 2 (<= 4 live paths; no ops: the decode kernel
+    // resumes from stage 1).
+    struct PrefixStage {
+        int nops = 0;          // the stage's ops in pfx_mops, after the earlier stages'
+        int rec = 0, pm = 0;   // words per path record, metric word in it
+        int paths = 1;         // paths per frame: the stage's list size and lanes per frame
+        DeviceBuf buf;         // the stage's records (interleaved, see FastPlan::pfx)
+        size_t cap = 0;
+        const void *patched = nullptr;  // the buffer address the device copies of the import ops hold
+    } pfx[3];
+    int prefix_ops() const { return pfx[0].nops + pfx[1].nops + pfx[2].nops; }
     std::vector<qpd::MOp> pfx_ops_host, main_ops_host;  // host copies of the split schedule (patch_imports)
-    const void *xin_at[3] = {nullptr, nullptr, nullptr};         // the buffer addresses the device copies hold
     std::vector<Op> ops_host;
     DeviceBuf lut_f, f_base, lut_g, g_base, vcl, ops, info_pos, scratch, err;
     DeviceBuf r_f, r_g, q_bnd, q_rec, bnd_off, bnd_len, rec_off, rec_len;  // float-domain re-quantizers
@@ -314,15 +318,21 @@ int validate(const qpd_config *c, int *n_out, int *fam_out, int *dom_out) {
 }
 
 
-// Point the import ops of a prefix-split schedule at the stage buffers (op.node: 1 / 2 /
-// 3 = stage 1b), on the launch stream, when a buffer moved.
+// The stage whose records an import op reads, from the planner's encoding in op.node
+// (plan_prefix in qpd_plan.hpp; tests/test_plan.py pins it): 1 = stage 1, 2 = stage 2,
+// 3 = stage 1b -- not the stages' order in qpd_decoder::pfx.
+int import_stage(const qpd::MOp &m) { return m.node == 3 ? 1 : m.node == 2 ? 2 : 0; }
+
+// Point the import ops of a prefix-split schedule at the stage buffers, on the launch
+// stream, when a buffer moved.
 int patch_imports(qpd_decoder *d, hipStream_t st) {
-    const void *b1 = d->pfx1_buf.p, *b2 = d->pfx2_buf.p, *b3 = d->pfx1b_buf.p;
-    if (d->xin_at[0] == b1 && d->xin_at[1] == b2 && d->xin_at[2] == b3) return QPD_OK;
+    bool moved = false;
+    for (const auto &sg : d->pfx) moved = moved || sg.patched != sg.buf.p;
+    if (!moved) return QPD_OK;
     auto patch = [&](std::vector<qpd::MOp> &v) {
         for (qpd::MOp &m : v)
             if (m.type == qpd::OP_IMPORT && (m.flags & qpd::MF_XBUF)) {
-                const uint64_t a = (uint64_t)(uintptr_t)(m.node == 3 ? b3 : m.node == 2 ? b2 : b1);
+                const uint64_t a = (uint64_t)(uintptr_t)d->pfx[import_stage(m)].buf.p;
                 m.u_row = (int32_t)(uint32_t)a;
                 m.r_row = (int32_t)(uint32_t)(a >> 32);
             }
@@ -333,9 +343,7 @@ int patch_imports(qpd_decoder *d, hipStream_t st) {
                            hipMemcpyHostToDevice, st));
     QPD_HIP(hipMemcpyAsync(d->mops.p, d->main_ops_host.data(), d->main_ops_host.size() * sizeof(qpd::MOp),
                            hipMemcpyHostToDevice, st));
-    d->xin_at[0] = b1;
-    d->xin_at[1] = b2;
-    d->xin_at[2] = b3;
+    for (auto &sg : d->pfx) sg.patched = sg.buf.p;
     return QPD_OK;
 }
 
@@ -399,7 +407,7 @@ unsigned long long *stamp_buffer() {  // one per device (the current one)
 #endif
 
 // The kernel must declare no static LDS: the byte tables' lookups address LDS
-// offset 0 as the start of the dynamic allocation (qpd_fast.hip lut_lds).
+// offset 0 as the start of the dynamic allocation (qpd_fast_lookup.hpp lut_lds).
 int check_no_static_lds(const void *kfn, const char *what) {
     hipFuncAttributes fa;
     QPD_HIP(hipFuncGetAttributes(&fa, kfn));
@@ -443,14 +451,13 @@ int build_fast(qpd_decoder *d, const qpd_config *c, const Schedule &s) {
     d->pw1 = H.pw1;
     d->pre = H.pre;
     d->pre_chunk = H.pre_chunk;
-    d->pfx_nops = (int)H.pfx[0].size();
-    d->pfx1b_nops = (int)H.pfx[1].size();
-    d->pfx2_nops = (int)H.pfx[2].size();
-    d->pfx1_rec = H.pfx_rec[0], d->pfx1_pm = H.pfx_pm[0];
-    d->pfx1b_rec = H.pfx_rec[1], d->pfx1b_pm = H.pfx_pm[1];
-    d->pfx2_rec = H.pfx_rec[2], d->pfx2_pm = H.pfx_pm[2];
+    for (int i = 0; i < 3; ++i) {
+        d->pfx[i].nops = (int)H.pfx[i].size();
+        d->pfx[i].rec = H.pfx_rec[i], d->pfx[i].pm = H.pfx_pm[i];
+        d->pfx[i].paths = 1 << i;  // 1, 2, 4
+    }
     F.nops = (int)H.ops.size();
-    d->num_mops = F.nops + d->pfx_nops + d->pfx1b_nops + d->pfx2_nops;
+    d->num_mops = F.nops + d->prefix_ops();
     if ((rc = upload(d->r1_rank, H.r1tab.data(), H.r1tab.size(), d->hs))) return rc;
     for (const auto &st : H.pfx)  // one device array: stage 1, stage 1b, then stage 2
         d->pfx_ops_host.insert(d->pfx_ops_host.end(), st.begin(), st.end());
@@ -465,7 +472,7 @@ int build_fast(qpd_decoder *d, const qpd_config *c, const Schedule &s) {
     if (!kfn) return fail(QPD_E_UNSUPPORTED, "fast plan: no decode kernel instantiation for this plan");
     if ((rc = check_no_static_lds(kfn, "fast decode kernel"))) return rc;
     // (the prefix stages' two-set instantiations do the same offset-0 byte-table lookups)
-    if (d->pfx_nops > 0 && d->pfx_sets == 2 &&
+    if (d->pfx[0].nops > 0 && d->pfx_sets == 2 &&
         (rc = check_no_static_lds(prefix_kernel(d->kind, d->pfx_sets, d->pw1), "fast prefix kernel")))
         return rc;
     // Persistent grid: as many waves as can be resident at once.
@@ -803,7 +810,7 @@ int qpd_get_info(const qpd_decoder *d, qpd_info *info) {
     info->engine = d->engine;
     info->lds_bytes_per_wave = d->lds_bytes;
     info->lds_from_depth = d->engine == QPD_ENGINE_FAST ? d->fplan.lds_from : -1;
-    info->prefix_ops = d->engine == QPD_ENGINE_FAST ? d->pfx_nops + d->pfx1b_nops + d->pfx2_nops : 0;
+    info->prefix_ops = d->engine == QPD_ENGINE_FAST ? d->prefix_ops() : 0;
     info->last_engine = d->last_engine;
     // f / g ops of a node at depth d look up N >> (d + 1) symbols each; a leaf
     // pair's two decisions one each (SCLLUTDecoder.cpp:83-89, :157-164)
@@ -852,54 +859,37 @@ int fast_launch(qpd_decoder *d, qpd::FastPlan fp, const int32_t *in, int64_t Bc,
     return rc;
 }
 
+// FastPlan::pfx_geo of a prefix stage with 2^ps paths per frame: 64 >> ps frames of 2^ps paths per 64 words.
+constexpr int prefix_geo(int ps) { return (6 - ps) | (ps << 8); }
+static_assert(prefix_geo(0) == 6 && prefix_geo(1) == (5 | (1 << 8)) && prefix_geo(2) == (4 | (2 << 8)), "stages 1, 1b, 2");
+
 // The decode of Bc frames from their root pre-pass rows (pre-mode decoders).
 int decode_pre_rows(qpd_decoder *d, const uint32_t *rows, int64_t Bc, uint8_t *out, hipStream_t st) {
     qpd::FastPlan fp = d->fplan;
     fp.in_vec = 1;
     fp.in_shift = fp.n - 2;
-    if (d->pfx_nops > 0) {  // the frozen-prefix stages, then the decode
-        int rc = ensure_records(d->pfx1_buf, d->pfx1_cap, Bc, d->pfx1_rec, 1);
-        if (!rc && d->pfx1b_nops > 0) rc = ensure_records(d->pfx1b_buf, d->pfx1b_cap, Bc, d->pfx1b_rec, 2);
-        if (!rc && d->pfx2_nops > 0) rc = ensure_records(d->pfx2_buf, d->pfx2_cap, Bc, d->pfx2_rec, 4);
+    if (d->pfx[0].nops > 0) {  // the frozen-prefix stages, then the decode
+        int rc = QPD_OK;
+        for (auto &sg : d->pfx)
+            if (!rc && sg.nops > 0) rc = ensure_records(sg.buf, sg.cap, Bc, sg.rec, sg.paths);
         if (!rc) rc = patch_imports(d, st);
         if (rc) return rc;
-        qpd::FastPlan pp = fp;  // stage 1: one path per frame
-        pp.ops = (const qpd::MOp *)d->pfx_mops.p;
-        pp.nops = d->pfx_nops;
-        pp.gs = 1;
-        pp.fpw = 64;
-        pp.L = 1;
-        pp.pfx = (uint32_t *)d->pfx1_buf.p;
-        pp.pfx_rec = d->pfx1_rec;
-        pp.pfx_geo = 6;
-        pp.pm_off = d->pfx1_pm;
-        rc = fast_launch(d, pp, (const int32_t *)rows, Bc, nullptr, st, true);
-        if (rc) return rc;
-        if (d->pfx1b_nops > 0) {  // stage 1b: <= 2 live paths, L = 2
-            pp.ops = (const qpd::MOp *)d->pfx_mops.p + d->pfx_nops;
-            pp.nops = d->pfx1b_nops;
-            pp.gs = 2;
-            pp.fpw = 32;
-            pp.L = 2;
-            pp.pfx = (uint32_t *)d->pfx1b_buf.p;
-            pp.pfx_rec = d->pfx1b_rec;
-            pp.pfx_geo = 5 | (1 << 8);
-            pp.pm_off = d->pfx1b_pm;
-            rc = fast_launch(d, pp, (const int32_t *)rows, Bc, nullptr, st, true);
-            if (rc) return rc;
-        }
-        if (d->pfx2_nops > 0) {  // stage 2: <= 4 live paths, L = 4
-            pp.ops = (const qpd::MOp *)d->pfx_mops.p + d->pfx_nops + d->pfx1b_nops;
-            pp.nops = d->pfx2_nops;
-            pp.gs = 4;
-            pp.fpw = 16;
-            pp.L = 4;
-            pp.pfx = (uint32_t *)d->pfx2_buf.p;
-            pp.pfx_rec = d->pfx2_rec;
-            pp.pfx_geo = 4 | (2 << 8);
-            pp.pm_off = d->pfx2_pm;
-            rc = fast_launch(d, pp, (const int32_t *)rows, Bc, nullptr, st, true);
-            if (rc) return rc;
+        qpd::FastPlan pp = fp;
+        const qpd::MOp *ops = (const qpd::MOp *)d->pfx_mops.p;
+        for (const auto &sg : d->pfx) {  // each stage with ops: `paths` lanes and list entries per frame
+            if (sg.nops > 0) {
+                const int ps = __builtin_ctz(sg.paths);
+                pp.ops = ops;
+                pp.nops = sg.nops;
+                pp.gs = pp.L = sg.paths;
+                pp.fpw = 64 >> ps;
+                pp.pfx = (uint32_t *)sg.buf.p;
+                pp.pfx_rec = sg.rec;
+                pp.pfx_geo = prefix_geo(ps);
+                pp.pm_off = sg.pm;
+                if ((rc = fast_launch(d, pp, (const int32_t *)rows, Bc, nullptr, st, true))) return rc;
+            }
+            ops += sg.nops;
         }
     }
     return fast_launch(d, fp, (const int32_t *)rows, Bc, out, st);

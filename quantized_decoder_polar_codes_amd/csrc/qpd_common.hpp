@@ -43,10 +43,10 @@ __device__ __forceinline__ uint64_t ptr_set(uint64_t p, int d, int lane_in_group
 // Lane `src` (0..63, taken mod 64) of x: one ds_bpermute at byte address
 // src * 4.  HIP's __shfl computes the same read but first rebuilds the lane id
 // (two mbcnt) and re-bases the source on it; the wave is 64 wide, so there is
-// nothing to re-base (SCL-LUT +0.7 %, profiles/r03t_ab_lane_read.txt).  The
-// FastSCL-LUT unit (qpd_fast_fscl.hip) keeps __shfl (QPD_LANE_READ_SHFL): there
-// the change moves its register allocation and costs 12 %.  Internal linkage,
-// so the two units' definitions stay separate.
+// nothing to re-base (SCL-LUT +0.7 %, profiles/r03t_ab_lane_read.txt).
+// QPD_LANE_READ_SHFL (a -D switch for A/B builds; no unit sets it) keeps the
+// __shfl form.  Internal linkage, so units built with either form keep their
+// definitions separate.
 #ifdef QPD_LANE_READ_SHFL
 static __device__ __forceinline__ uint32_t lane_read(uint32_t x, int src) { return __shfl(x, src); }
 static __device__ __forceinline__ int lane_read(int x, int src) { return __shfl(x, src); }

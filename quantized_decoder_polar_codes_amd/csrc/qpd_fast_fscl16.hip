@@ -4,7 +4,6 @@
 // layer; R1 nodes of up to 15 layers), with two or one pointer words per path.
 // A unit of its own: it compiles beside the others and leaves their objects as
 // they are.  See qpd_k_fast.hip for the units.
-#define QPD_FAST_TEMPLATES_ONLY
 #ifndef QPD_VEC_CHAIN  // as the other FastSCL-LUT units (qpd_fast_fscl.hip)
 #define QPD_VEC_CHAIN 1
 #endif

@@ -1,0 +1,64 @@
+// qpd_fast_pre.hpp -- the fast engine's root pre-pass kernel (pre-mode), launched
+// by qpd_capi.hip before the decode kernels of qpd_fast.hip.
+#pragma once
+#include "qpd_fast_switches.hpp"
+
+#include "qpd_fast_lookup.hpp"
+
+namespace qpd {
+
+// ---------------------------------------------------------------------------
+// Root pre-pass (pre-mode: N >= 16, the root's left child a plain node).
+// The root's f and both g variants depend on the channel symbols only, yet
+// every path of a frame computes them (SCLLUTDecoder.cpp:83-89 / :157-164 at
+// depth 0: L x N lookups per frame), and the decode kernel would read the
+// frame's 4 KB of int32 symbols twice, half a decode apart.  Here one thread
+// per output word computes them once per frame from one coalesced read of the
+// channel, into a row of N/4 words per frame: [f(y) | g(y, 0) | g(y, 1) | -],
+// N/16 words each, 8 nibble symbols per word as S[1].  The decode kernel then
+// reads the left child's S[1] from the row (MF_PRE) and builds the root g by
+// nibble selects (MF_GSEL, gsel_op).  Out-of-range symbols raise the error
+// flag here, as chan_word8 does in the decode kernel.
+// ---------------------------------------------------------------------------
+// The root's f and g tables as bytes in LDS once per block (stage_tab): an
+// element's 8-bit index addresses all three results (f, g with u = 0 at +0,
+// u = 1 at +256) -- one field extract and three ds_read_u8 per element.
+__global__ __launch_bounds__(256) void root_pre_kernel(FastPlan P, const int32_t *__restrict__ in, int64_t B,
+                                                       uint32_t *__restrict__ pre) {
+    __shared__ __attribute__((aligned(16))) uint8_t tf[256], tg[512];
+    if (threadIdx.x < 64) {  // node 0 (posi 0)
+        stage_tab(tg, P.g_tab[threadIdx.x], threadIdx.x);
+        if (threadIdx.x < 32) stage_tab(tf, P.f_tab[threadIdx.x], threadIdx.x);
+    }
+    __syncthreads();
+    const int wsh = P.n - 4;  // log2 words per segment
+    const int half = P.N >> 1;
+    const int64_t total = B << wsh;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < total; base += (int64_t)gridDim.x * 256) {
+        const int64_t t0 = base + threadIdx.x;
+        const int64_t t = t0 < total ? t0 : total - 1;
+        const int64_t f = t >> wsh;
+        const int w = (int)(t & ((1 << wsh) - 1));
+        const int32_t *y = in + (f << P.n);
+        const uint32_t a = chan_word8(y, 8 * w, P.in_vec, P.v, P.err);
+        const uint32_t b = chan_word8(y, half + 8 * w, P.in_vec, P.v, P.err);
+        const uint32_t X = ((a << 4) & 0xF0F0F0F0u) | (b & 0x0F0F0F0Fu);  // byte j: index of element 2j
+        const uint32_t Y = (a & 0xF0F0F0F0u) | ((b >> 4) & 0x0F0F0F0Fu);  // ... of element 2j + 1
+        uint32_t fw = 0, g0 = 0, g1 = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t idx = __builtin_amdgcn_ubfe((k & 1) ? Y : X, 8 * (k >> 1), 8);
+            fw |= (uint32_t)tf[idx] << (4 * k);
+            g0 |= (uint32_t)tg[idx] << (4 * k);
+            g1 |= (uint32_t)tg[256 + idx] << (4 * k);
+        }
+        if (t0 < total) {
+            uint32_t *row = pre + (f << (P.n - 2));
+            row[w] = fw;
+            row[(1 << wsh) + w] = g0;
+            row[(2 << wsh) + w] = g1;
+        }
+    }
+}
+
+}  // namespace qpd

@@ -1,7 +1,6 @@
 // qpd_k_scl.hip -- SCL-LUT decode kernel instantiations with two pointer words
 // per path (lut_fast_kernel<K_SCL_LUT, NS, L8>, qpd_fast.hip; see qpd_k_fast.hip);
 // w16: list sizes 9..16 (W16, lane groups of 16).
-#define QPD_FAST_TEMPLATES_ONLY
 #include "qpd_fast.hip"
 #include "qpd.h"
 

@@ -2,7 +2,6 @@
 // per path (lut_fast_kernel<K_SCL_LUT, NS, L8, false, false, PW1 = true>,
 // qpd_fast.hip; see qpd_k_fast.hip).  The bench workload's kernel; w16: list sizes
 // 9..16 (W16).
-#define QPD_FAST_TEMPLATES_ONLY
 #include "qpd_fast.hip"
 #include "qpd.h"
 

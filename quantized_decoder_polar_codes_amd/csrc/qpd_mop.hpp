@@ -73,7 +73,7 @@ struct MOp {
 constexpr int kSelInts = 128;  // per set: 64 slots + 64 junk slots (select_survivors8): two rows after the set's
 
 // QPD_LEAF_T = 1 -- the depth n-1 tables are stored transposed (entry
-// u * 256 + b * 16 + a: pack_tables in qpd_plan.hpp, leaf_idx in qpd_fast.hip).
+// u * 256 + b * 16 + a: pack_tables in qpd_plan.hpp, leaf_idx in qpd_fast_bot.hpp).
 #ifndef QPD_LEAF_T
 #define QPD_LEAF_T 1
 #endif

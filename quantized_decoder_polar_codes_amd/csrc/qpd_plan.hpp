@@ -144,10 +144,10 @@ inline bool quanta_uniform(const double *vcl, int N, int v, int d, int node) {
     return true;
 }
 
-// A height-3 subtree under (d = n-3, node) that botx_op (qpd_fast.hip) can run in
+// A height-3 subtree under (d = n-3, node) that botx_op (qpd_fast_bot.hpp) can run in
 // registers: its nodes of size 4 and 2 plain or FastSCL special nodes (R0 / R1 /
 // REP) with one quanta row each.  *ty = the types, two bits per node (q1, q2,
-// then q3..q6; BX_* in qpd_fast.hip).
+// then q3..q6; BX_* in qpd_fast_bot.hpp).
 inline bool bot3_mixed(const PlanSwitches &sw, int kind, const int32_t *node_type, const double *vcl, int N, int n, int v, int node,
                        int *ty) {
     if (kind != QPD_FASTSCL_LUT || n < 4 || v > 16) return false;
@@ -297,7 +297,7 @@ inline void fast_ops(std::vector<qpd::MOp> &out, const FastLayout &Ly, const Pla
                    (Ly.botx && bot3_mixed(sw, kind, node_type, vcl, N, n, v, c, &t0));
         };
         // FastSCL-LUT (L = 8): a size-8 special child takes this node's f / g and combine too
-        // (MF_SFG / MF_SGG / MF_SCOMB: r0rep_multi, r1_multi in qpd_fast.hip); R1 only with its
+        // (MF_SFG / MF_SGG / MF_SCOMB: r0rep_multi, r1_multi in qpd_fast_special.hpp); R1 only with its
         // ranks in the op record (MF_R1_RK: the record's tab field then holds this node's table)
         auto spec8_able = [&](int c) {
             const int cp = (1 << (d + 1)) + c - 1, ts = special_of(kind, node_type, cp);
@@ -393,7 +393,7 @@ inline void fast_ops(std::vector<qpd::MOp> &out, const FastLayout &Ly, const Pla
 }
 
 // Fold an F at depth d+1 into the F / G right before it that produced its
-// input (MF_FF, ff_op in qpd_fast.hip): the child's f reads the words the
+// input (MF_FF, ff_op in qpd_fast_lookup.hpp): the child's f reads the words the
 // parent just computed from registers instead of re-reading S[d+1] from the
 // slab.  Pairs are taken greedily down each descent (G1+F2, F3+F4, ...);
 // S[d] and S[d+1] as the slab rows ff_op reads, S[d+1] of at least 4 words.
@@ -427,7 +427,7 @@ inline void fuse_descent(std::vector<qpd::MOp> &ops) {
 }
 
 // Fold the combine at depth n-5 into the right BOT3 before it (MF_BC2, the
-// end of bot3_op in qpd_fast.hip): a right BOT3 that already runs its
+// end of bot3_op in qpd_fast_bot.hpp): a right BOT3 that already runs its
 // parent's combine (MF_BCOMB) and writes R[n-4] is followed by the COMB that
 // reads that row and its left sibling's U[n-4]; the BOT3 computes that
 // combine from its result in registers and writes the COMB's destination, so
@@ -520,7 +520,7 @@ struct FastOwner {
 };
 
 // Rows of the fast engine's slab / LDS an op reads and writes (space, first
-// row, count), from the access pattern of its code in qpd_fast.hip.  Reads of
+// row, count), from the access pattern of its code in qpd_fast.hip and its headers.  Reads of
 // the channel or a pre-pass row (MF_CHAN / MF_PRE) are not row reads.
 template <class Fn>
 void op_rows(const qpd::MOp &m, Fn &&acc) {
@@ -815,7 +815,7 @@ void pointer_fields(qpd::MOp &m, int &bc_u, int &bc_dst, Fn &&fn) {
     }
 }
 
-// One pointer word per path (PathT<true>, qpd_fast.hip): the pointer fields
+// One pointer word per path (PathT<true>, qpd_fast_select.hpp): the pointer fields
 // the op lists use (pointer_fields), packed into consecutive 4-bit positions
 // of one word.  False (lists unchanged) when they need more than 16 fields.
 inline bool compact_pointer_fields(const std::vector<std::vector<qpd::MOp> *> &lists) {
@@ -877,7 +877,7 @@ inline FastOwner make_owner(const FastLayout &Ly, const bool (&use)[3][qpd::kMax
 
 // Nibble-packed tables: entry (u, a, b) of node p at bit 4*(idx&7) of dword idx>>3, idx =
 // u * 256 + a * 16 + b; the leaf pairs' nodes (depth n-1: only the leaf lookups read them)
-// transposed, idx = u * 256 + b * 16 + a (qpd_fast.hip leaf_idx, QPD_LEAF_T)
+// transposed, idx = u * 256 + b * 16 + a (qpd_fast_bot.hpp leaf_idx, QPD_LEAF_T)
 inline void pack_tables(const qpd_config &c, std::vector<uint32_t> &ft, std::vector<uint32_t> &gt) {
     const int N = c.N, v = c.v;
     ft.assign((size_t)(N - 1) * 32, 0);
@@ -971,7 +971,7 @@ inline int plan_fast(const qpd_config &c, int n, int L, const Schedule &s, const
         std::memcpy(use, used, sizeof(use));
     }
     // the list kinds' byte tables of the f / g ops at two frame sets (stage_tab in
-    // qpd_fast.hip: 512 B for the op's table, 256 B for a folded child's f), at LDS
+    // qpd_fast_lookup.hpp: 512 B for the op's table, 256 B for a folded child's f), at LDS
     // offset 0: before the sets' rows and selection scratch (lut_lds)
     P.lds_tab_bytes = list_kind && NS >= 2 ? 768 : 0;
     // LDS per wave = NS * (selection scratch + rows of depths >= D) + the byte

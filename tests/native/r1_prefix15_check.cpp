@@ -1,5 +1,5 @@
 // Host check of the R1 argsort of the fast kernel for up to 15 survivor layers
-// (qpd_fast.hip r1_prep with the layer bound 15: FastSCL-LUT, L = 9..16).  An R1
+// (qpd_fast_special.hpp r1_prep with the layer bound 15: FastSCL-LUT, L = 9..16).  An R1
 // node of n <= 32 elements sorts its |llr| with std::sort on an index array and a
 // keys-only comparison (argsort, FastSCLLUTDecoder.cpp:7-17) and reads the first
 // m = min(L - 1, n) outputs.  The kernel holds 16-bit entries rank << 5 | element

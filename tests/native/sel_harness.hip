@@ -1,5 +1,5 @@
 // Device harness of the list decoders' 2L -> L survivor selection: one small kernel
-// that calls the selection primitives of qpd_fast.hip / qpd_common.hpp directly, on
+// that calls the selection primitives of qpd_fast_select.hpp / qpd_common.hpp directly, on
 // keys the caller chooses per lane, with the LDS laid out as lut_fast_kernel lays it
 // out (set s's 64 slots at sel_all + 64 * s, its junk row NS * 64 words on) between
 // two rows of canary words.  tests/test_gpu_selection.py compares what it returns
@@ -9,8 +9,9 @@
 //
 // A checker, not a stress tool: the entry point refuses every L and set count the
 // decode kernels cannot run (L outside 1..16, more than 2 sets) before it launches.
-#define QPD_FAST_TEMPLATES_ONLY
-#include "qpd_fast.hip"
+#include "qpd_fast_select.hpp"
+#include "qpd_common.hpp"
+#include "qpd_mop.hpp"  // kSelInts
 
 #include <algorithm>
 #include <vector>

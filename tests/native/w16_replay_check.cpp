@@ -1,4 +1,4 @@
-// Scalar emulation of the W16 survivor selection (qpd_fast.hip select_survivors16:
+// Scalar emulation of the W16 survivor selection (qpd_fast_select.hpp select_survivors16:
 // dense key ranks, the group-parallel replay of stl::partition_prefix by scan-stop
 // masks and all of a partition's swaps at once (stop ranks and slots), and the
 // final (rank, position) selection), step for step as one lane group runs it,

@@ -1,5 +1,5 @@
 """FastSCL-LUT height-3 subtrees with special nodes in registers (BOTX:
-qpd_capi.hip bot3_mixed, qpd_fast.hip botx_op / bx_spec).  A subtree whose
+qpd_plan.hpp bot3_mixed, qpd_fast_bot.hpp botx_op / bx_spec).  A subtree whose
 size-4 / size-2 nodes are R0 / R1 / REP nodes (FastSCLLUTDecoder.cpp:83-213)
 runs as one op; its bits must equal the interpreted schedule's
 (QPD_NO_BOTX=1) and the oracle's, for every mix of node types (random

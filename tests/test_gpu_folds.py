@@ -1,5 +1,5 @@
 """Folded ops of the SCL-LUT schedule (qpd_plan.hpp: fuse_descent, fold_combine;
-qpd_fast.hip: ff_op, the MF_BC2 end of bot3_op).  An F / G op that also runs
+qpd_fast_lookup.hpp: ff_op; qpd_fast_bot.hpp: the MF_BC2 end of bot3_op).  An F / G op that also runs
 its left child's f from registers, and a right BOT3 that also runs its
 grandparent's combine, must give the bits of the unfolded schedule
 (QPD_NO_FF=1 QPD_NO_BC2=1) and the oracle's, whatever row spaces the layout

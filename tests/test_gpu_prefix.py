@@ -115,6 +115,27 @@ def test_prefix_stage1b(N, K, L, qpd, oracle_mod, monkeypatch):
     assert_frames_equal(ga[rows], want, a, f"prefix-1b-{N}-{K}-{L}")
 
 
+def test_prefix_all_stages_grown_records(qpd, oracle_mod, monkeypatch):
+    """Stages 1, 1b and 2 on one handle, 64 frames and then 4096: the second call
+    reallocates every stage's record buffer, so the import ops of stage 1b, stage 2
+    and the decode kernel are patched again, each to its own stage's new buffer.
+    N = 128, K = 48: the smallest PW code at L = 8 whose plan puts ops in all three
+    stages (the plan compiler on the CPU: 7 / 12 / 10 ops; K = 64 gets no stage 1b)."""
+    N, K, L = 128, 48, 8
+    fm, nt = _code(N, K)
+    p = _tables(N, 1248)
+    sym = np.random.default_rng(1248).integers(0, 16, size=(4096, N), dtype=np.int32)
+    sym[:1024] = np.clip(sym[:1024] // 2 + 8, 0, 15)
+    monkeypatch.setenv("QPD_PFX1B", "1")
+    a = _make(qpd, monkeypatch, "SCL-LUT", p, K, fm, L, nt, True)
+    monkeypatch.delenv("QPD_PFX1B", raising=False)
+    c = _make(qpd, monkeypatch, "SCL-LUT", p, K, fm, L, nt, True)
+    assert a.info()["prefix_ops"] > c.info()["prefix_ops"] > 0  # stage 1b taken
+    want = oracle_mod.decode_lut("SCL-LUT", p, K, L, fm, sym, node_type=nt)
+    assert_frames_equal(a.decode_batch(sym[:64]), want[:64], a, "prefix-grow-64")
+    assert_frames_equal(a.decode_batch(sym), want, a, "prefix-grow-4096")
+
+
 @pytest.mark.parametrize("N,K", [(64, 64), (1024, 1024), (1024, 16)])
 def test_prefix_edge_codes_exact(N, K, qpd, oracle_mod, monkeypatch):
     """Every bit information (K = N: the prefix is only the f ops down to the

@@ -1,4 +1,4 @@
-"""SCL-LUT with 9 <= L <= 16 on the fast engine (lane groups of 16: qpd_fast.hip
+"""SCL-LUT with 9 <= L <= 16 on the fast engine (lane groups of 16: qpd_fast_select.hpp
 keep_all16 / select_survivors16, W16 instantiations).
 
 mink (SCLLUTDecoder.cpp:8-21) sorts 2L > 16 candidates there, so libstdc++ runs

@@ -1,5 +1,5 @@
 """The R1 argsort of the fast kernel with up to 15 survivor layers (FastSCL-LUT, L = 9..16;
-qpd_fast.hip r1_prep): both of its paths -- the min-tree pick for nodes of <= 16 elements, and
+qpd_fast_special.hpp r1_prep): both of its paths -- the min-tree pick for nodes of <= 16 elements, and
 stl::partition_prefix plus the m smallest (rank, position) for 17..32 -- give the first m outputs
 of std::sort with a keys-only comparison, m = 1..15, heap-sort fallbacks included."""
 import os

@@ -17,7 +17,7 @@ def test_stl_sort_matches_std_sort(tmp_path):
 
 
 def test_w16_parallel_replay_matches_std_sort(tmp_path):
-    """The W16 kernel's survivor selection for 2L > 16 candidates (qpd_fast.hip
+    """The W16 kernel's survivor selection for 2L > 16 candidates (qpd_fast_select.hpp
     select_survivors16: dense ranks, the introsort partitions replayed from
     scan-stop masks, the final (rank, position) selection), emulated lane group
     by lane group, gives std::sort's first L outputs (mink, H1) on tie-heavy

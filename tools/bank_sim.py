@@ -1,5 +1,5 @@
 """Diagnostic: LDS bank conflicts of the f / g byte-table lookups (lut_lds in
-qpd_fast.hip) under alternative table layouts, simulated on the bench workload.
+qpd_fast_lookup.hpp) under alternative table layouts, simulated on the bench workload.
 
 The host engine records every f / g element lookup (u, a, b) of the tree depths
 the GPU's F / G ops look up from the byte tables (1 <= d <= n-4); lookups are

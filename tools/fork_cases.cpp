@@ -19,7 +19,7 @@ static void fork_hook(const double *key, int L) {
     int c = 2;
     if (sorted && below == 0) c = 0;
     else if (sorted && below == 1 && key[L + a] >= key[L - 2]) c = 1;
-    // 2L > 16 (the W16 kernel, qpd_fast.hip select_survivors16): strict identity, and a tie
+    // 2L > 16 (the W16 kernel, qpd_fast_select.hpp select_survivors16): strict identity, and a tie
     // among the first L stable ranks (the introsort replay)
     bool strict = true;
     for (int j = 0; j + 1 < L; ++j) strict = strict && key[j] < key[j + 1];
