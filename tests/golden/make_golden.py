@@ -66,11 +66,16 @@ def ref_decode(R, kind, N, K, L, frozen, msgmask, node_type, packed, sym):
     return np.stack([d.decode(s.astype(np.int32)) for s in sym]).astype(np.uint8)
 
 
-def make_lut_case(R, name, kind, N, K, L, lut_kind, B, ebn0, seed):
+def make_lut_case(R, name, kind, N, K, L, lut_kind, B, ebn0, seed, v=16, frozen=None):
+    """`frozen`: a frozen mask with K zeros in place of the 5G PW order's (tests/code_masks.py)."""
     rng = np.random.default_rng(seed)
-    _, msgbits, frozen, msgmask = C.construct_pw(N, K)
+    if frozen is None:
+        _, msgbits, frozen, msgmask = C.construct_pw(N, K)
+    else:
+        assert int((frozen == 0).sum()) == K
+        msgbits, msgmask = np.flatnonzero(frozen == 0), 1 - frozen
     node_type = C.identify_nodes(N, msgbits).astype(np.int32)
-    v, delta = 16, 0.5
+    delta = 0.5
     if lut_kind == "minsum":
         packed = LU.minsum_uniform_luts(N, v=v, delta=delta)
     else:
@@ -219,6 +224,23 @@ def main_wide():
     make_ca_case(R, "ca_fastscllut_n128_a40_l32_random", "CA-FastSCL-LUT", 128, 40, 32, "random", 150, 1.5, 40)
 
 
+def main_alphabet_masks():
+    """Away from v = 16 and the PW order: v = 8 on the PW mask, and v = 16 on a block-structured mask (R1
+    before R0, special nodes in an order no reliability sequence gives; tests/code_masks.py)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import code_masks as M
+
+    R = O.reference_module()
+    if R is None:
+        raise SystemExit("oracle/_ref not built (run oracle/build_ref.sh)")
+    make_lut_case(R, "scllut_n128_k64_l8_v8_random", "SCL-LUT", 128, 64, 8, "random", 64, 2.0, 41, v=8)
+    make_lut_case(R, "fastscllut_n128_k64_l8_v8_random", "FastSCL-LUT", 128, 64, 8, "random", 64, 2.0, 42, v=8)
+    fm = M.block_mask(128, 5)
+    K = int((fm == 0).sum())
+    make_lut_case(R, f"scllut_n128_k{K}_l8_block5_random", "SCL-LUT", 128, K, 8, "random", 64, 2.0, 43, frozen=fm)
+    make_lut_case(R, f"fastscllut_n128_k{K}_l8_block5_random", "FastSCL-LUT", 128, K, 8, "random", 64, 2.0, 44, frozen=fm)
+
+
 def main_md():
     R = O.reference_module()
     if R is None:
@@ -235,8 +257,11 @@ if __name__ == "__main__":
         main_md()  # only the MinDistortion (BASELINE workload) fixtures
     elif sys.argv[1:] == ["wide"]:
         main_wide()  # only the L > 8 fixtures
+    elif sys.argv[1:] == ["alphabet_masks"]:
+        main_alphabet_masks()  # only the v = 8 and block-mask fixtures
     else:
         main()
         main_ca()
         main_md()
         main_wide()
+        main_alphabet_masks()

@@ -12,6 +12,9 @@ The sweep: every LUT kind; the 5G PW codes at N = 8 .. 1024 with a low, half
 and high rate, N = 2048 and 4096 with the BEC construction; L = 1 (SC kinds) or
 2, 4, 8, 12, 16; tie-heavy random tables and the MinDistortion tables of the
 committed goldens; each switch on its own and the LDS budgets the GPU tests use.
+Beside that point of the input space (v = 16, nested reliability orders): the
+alphabets 2, 3, 8 and 15, and the random, block-structured and edge masks of
+tests/code_masks.py at N = 8 .. 1024.
 """
 import ctypes
 import os
@@ -20,6 +23,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import code_masks as M
 from conftest import ROOT, GOLDEN_DIR, golden_packed, load_golden
 
 CSRC = os.path.join(ROOT, "quantized_decoder_polar_codes_amd", "csrc")
@@ -110,11 +114,15 @@ def rates(N):
     return sorted({max(1, N // 4), N // 2, 3 * N // 4})
 
 
-def sweep(harness, kind, N, K, packed, Ls, sweep_switches):
-    """Plans (kind, N, K) for every L and switch setting; the refusals as {(L, switch setting)}."""
+def sweep(harness, kind, N, K, packed, Ls, sweep_switches, fm=None):
+    """Plans (kind, N, K) for every L and switch setting; the refusals as {(L, switch setting)}.  `fm`: a
+    frozen mask with K zeros to plan instead of the reliability order's."""
     from quantized_decoder_polar_codes_amd import decoders as D
 
-    fm, nt = code(N, K)
+    if fm is None:
+        fm, nt = code(N, K)
+    else:
+        nt = M.node_type_of(fm)
     if kind.startswith("Fast") and 0 <= nt[0] <= (3 if kind == "FastSC-LUT" else 2):
         return None  # a special root is rejected by qpd_create's validation, before any plan
     refused, seen = set(), 0
@@ -150,6 +158,50 @@ def test_plan_invariants_random_tables(kind, N, harness):
     p = LU.random_luts(N, 16, seed=3 * N + 1, distinct_mags=3)
     for K in rates(N):
         sweep(harness, kind, N, K, p, list_sizes(kind), SWEEP)
+
+
+@pytest.mark.parametrize("v", [2, 3, 8, 15])
+@pytest.mark.parametrize("N", [8, 16, 32, 64, 128, 256, 512, 1024])
+@pytest.mark.parametrize("kind", KINDS)
+def test_plan_invariants_alphabets(kind, N, v, harness):
+    """Alphabets below 16 on the reliability order, per-element quanta and (node_rows) one row per node."""
+    from quantized_decoder_polar_codes_amd import lut as LU
+
+    seen = 0
+    for node_rows in (False, True):
+        p = LU.random_luts(N, v, seed=3 * N + v, distinct_mags=3, node_rows=node_rows)
+        for K in rates(N):
+            r = sweep(harness, kind, N, K, p, list_sizes(kind), SWEEP)
+            if r is not None:
+                seen |= r[1]
+    if kind.startswith("Fast") and N >= 64:
+        assert seen & MF_VUNI
+
+
+def mask_cases(N):
+    """(name, mask) of the three mask families at N."""
+    out = [(f"random{s}", M.random_mask(N, K, s)) for s, K in enumerate(rates(N))]
+    out += [(f"block{s}", M.block_mask(N, s)) for s in M.BLOCK_SEEDS.get(N, (3, 4, 5))]
+    return out + list(M.edge_masks(N).items())
+
+
+@pytest.mark.parametrize("v", [16, 8])
+@pytest.mark.parametrize("N", [8, 16, 32, 64, 128, 256, 512, 1024])
+@pytest.mark.parametrize("kind", KINDS)
+def test_plan_invariants_masks(kind, N, v, harness):
+    """Masks no reliability order gives: an empty frozen prefix, a frozen last position, R1 before R0, special
+    nodes of every size in any order.  The only refusal stays the W16 one (sweep asserts it)."""
+    from quantized_decoder_polar_codes_amd import lut as LU
+
+    p = LU.random_luts(N, v, seed=5 * N + v, distinct_mags=3, node_rows=True)
+    unplanned = set()
+    for name, fm in mask_cases(N):
+        r = sweep(harness, kind, N, int((fm == 0).sum()), p, list_sizes(kind), SWEEP, fm=fm)
+        assert (r is None) == M.special_root(fm, kind), name
+        if r is None:
+            unplanned.add(name)
+    if N >= 16:  # a special root, which qpd_create's validation rejects: all_info alone (at N = 8 a block mask may be one node)
+        assert unplanned == ({"all_info"} if kind.startswith("Fast") else set())
 
 
 @pytest.mark.parametrize("N,K", [(2048, 512), (2048, 1024), (2048, 1536), (4096, 1400), (4096, 2048), (4096, 3072)])
