@@ -39,6 +39,8 @@
  *                        src/SCLUniformQuantizedDecoder.cpp:43-184
  *                    SC{l,L}loydQuantizedDecoder::decode src/SCLloydQuantizedDecoder.cpp:22-101,
  *                        src/SCLLloydQuantizedDecoder.cpp:46-187
+ *   qpd_decode_u8 / qpd_decode_u8_host: qpd_decode / qpd_decode_host from uint8
+ *                   symbols (no reference counterpart: its array_t<int> is int32)
  *   qpd_decode_host / qpd_decode_f64_host: the same from host buffers
  *                   (copy in, decode, copy out, synchronous) -- what a
  *                   per-frame `decode(symbols)` call needs.
@@ -63,7 +65,7 @@
 extern "C" {
 #endif
 
-#define QPD_ABI_VERSION 6
+#define QPD_ABI_VERSION 7
 
 /* Decoder kinds (the reference's class names). */
 enum qpd_kind {
@@ -197,6 +199,15 @@ void qpd_destroy(qpd_decoder *dec);
  * py_SCLLUTDecoder.cpp:15); concurrent streams on ONE decoder do not overlap
  * -- use one decoder per stream for that. */
 int qpd_decode(qpd_decoder *dec, const int32_t *d_symbols, int64_t B, uint8_t *d_out, void *stream);
+/* The same from uint8 channel symbols (the alphabet is at most 256, and at most
+ * 16 on the fast engine): d_symbols is device uint8 [B][N], a quarter of the
+ * int32 input; same contract, stream ordering, range check (QPD_E_INPUT for a
+ * symbol >= v) and decoded bits as qpd_decode.  A fast-engine decoder in
+ * pre-mode reads the bytes as they are (the root pre-pass; fastest from an
+ * 8-byte-aligned buffer); every other decoder widens them, chunk by chunk, into
+ * an int32 staging buffer of its own (<= 1 GB) and runs the int32 launch
+ * (qpd_info.u8_staged). */
+int qpd_decode_u8(qpd_decoder *dec, const uint8_t *d_symbols, int64_t B, uint8_t *d_out, void *stream);
 /* float64-LLR kinds (QPD_SC_FLOAT, 7..14).  d_llr: device float64 [B][N];
  * d_out: device uint8 [B][K] ([B][A] for QPD_CASCL_FLOAT). */
 int qpd_decode_f64(qpd_decoder *dec, const double *d_llr, int64_t B, uint8_t *d_out, void *stream);
@@ -209,6 +220,7 @@ int qpd_decode_f64(qpd_decoder *dec, const double *d_llr, int64_t B, uint8_t *d_
  * a GPU call ~0.1 ms); larger batches on the GPU kernels.  Both decode the
  * same bits (the reference's). */
 int qpd_decode_host(qpd_decoder *dec, const int32_t *h_symbols, int64_t B, uint8_t *h_out);
+int qpd_decode_u8_host(qpd_decoder *dec, const uint8_t *h_symbols, int64_t B, uint8_t *h_out);
 int qpd_decode_f64_host(qpd_decoder *dec, const double *h_llr, int64_t B, uint8_t *h_out);
 
 /* Where the host-buffer calls run: AUTO (the default; the host engine up to
@@ -317,7 +329,9 @@ typedef struct qpd_info {
                                  the general special-node instantiation (R1L: R1 nodes
                                  beyond the LDS tail or without op-record ranks, R0 / REP
                                  nodes without one quanta row); 0 otherwise */
-    int32_t reserved0;
+    int32_t u8_staged;        /* 1: the handle's last decode call widened uint8 input into the
+                                 int32 staging buffer (qpd_decode_u8 / _u8_host outside pre-mode);
+                                 0: int32 and float64 calls, host-engine runs, uint8 read directly */
 } qpd_info;
 /* qpd_info.last_engine: no decode yet, the GPU kernels (qpd_decode*, the GPU
  * branch of the host-buffer calls, qpd_mc_decode), or the host engine. */

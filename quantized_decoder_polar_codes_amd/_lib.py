@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("QPD_LIB") or os.path.join(HERE, "libqpd.so")
  QPD_SCL_LLOYD) = range(15)
 FLOAT_KINDS = (QPD_SC_FLOAT, QPD_SCL_FLOAT, QPD_CASCL_FLOAT, QPD_FASTSC_FLOAT, QPD_FASTSCL_FLOAT, QPD_SC_UNIFORM,
                QPD_SCL_UNIFORM, QPD_SC_LLOYD, QPD_SCL_LLOYD)
-ABI_VERSION = 6
+ABI_VERSION = 7
 QPD_ENGINE_AUTO, QPD_ENGINE_GENERIC, QPD_ENGINE_FAST = range(3)
 QPD_OK, QPD_E_INVALID, QPD_E_UNSUPPORTED, QPD_E_DEVICE, QPD_E_INPUT = 0, -1, -2, -3, -4
 
@@ -29,8 +29,10 @@ EXPORTED = (
     "qpd_create",
     "qpd_destroy",
     "qpd_decode",
+    "qpd_decode_u8",
     "qpd_decode_f64",
     "qpd_decode_host",
+    "qpd_decode_u8_host",
     "qpd_decode_f64_host",
     "qpd_check_input_error",
     "qpd_get_info",
@@ -123,7 +125,7 @@ class QpdInfo(ctypes.Structure):
         ("last_engine", _i32),
         ("lookups_per_path", _i64),
         ("fast_variant", _i32),
-        ("reserved0", _i32),
+        ("u8_staged", _i32),
     ]
 
 
@@ -162,10 +164,14 @@ def load():
     L.qpd_destroy.restype = None
     L.qpd_decode.argtypes = [_P, _P, _i64, _P, _P]
     L.qpd_decode.restype = ctypes.c_int
+    L.qpd_decode_u8.argtypes = [_P, _P, _i64, _P, _P]
+    L.qpd_decode_u8.restype = ctypes.c_int
     L.qpd_decode_f64.argtypes = [_P, _P, _i64, _P, _P]
     L.qpd_decode_f64.restype = ctypes.c_int
     L.qpd_decode_host.argtypes = [_P, _P, _i64, _P]
     L.qpd_decode_host.restype = ctypes.c_int
+    L.qpd_decode_u8_host.argtypes = [_P, _P, _i64, _P]
+    L.qpd_decode_u8_host.restype = ctypes.c_int
     L.qpd_decode_f64_host.argtypes = [_P, _P, _i64, _P]
     L.qpd_decode_f64_host.restype = ctypes.c_int
     L.qpd_check_input_error.argtypes = [_P]

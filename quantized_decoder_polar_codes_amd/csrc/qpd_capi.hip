@@ -103,6 +103,11 @@ struct qpd_decoder {
     DeviceBuf mc_sym;        // qpd_mc_decode without a fused pre-pass: int32 symbols of one chunk
     int64_t mc_sym_cap = 0;  // frames mc_sym holds
     bool mc_sym_fell_back = false;
+    DeviceBuf u8_sym;        // qpd_decode_u8 outside pre-mode: int32 symbols of one chunk (widen_u8_kernel)
+    int64_t u8_cap = 0;      // frames u8_sym holds
+    int64_t u8_chunk = 0;    // QPD_U8_CHUNK (tests): frames per staging chunk (0: 1 GB of int32 symbols)
+    bool u8_fell_back = false;
+    int u8_staged = 0;       // qpd_info.u8_staged: the last decode call widened its input into u8_sym
     DevPlan plan{};
     qpd::FastPlan fplan{};
     DeviceBuf f_tab, g_tab, fscratch, mops, r1_rank, task_ctr;
@@ -634,6 +639,7 @@ int qpd_create(const qpd_config *cfg, qpd_decoder **out) {
         d->engine = want == QPD_ENGINE_FAST ? QPD_ENGINE_FAST
                     : (want == QPD_ENGINE_GENERIC || !fast_auto) ? QPD_ENGINE_GENERIC : QPD_ENGINE_FAST;
     }
+    if (const char *e = getenv("QPD_U8_CHUNK")) d->u8_chunk = std::max<int64_t>(1, atoll(e));
 
     DevPlan &P = d->plan;
     P.N = c->N;
@@ -820,7 +826,7 @@ int qpd_get_info(const qpd_decoder *d, qpd_info *info) {
         else if (o.type == qpd::OP_LEAF_L || o.type == qpd::OP_LEAF_R) lk += 1;
     info->lookups_per_path = lk;
     info->fast_variant = d->engine == QPD_ENGINE_FAST ? (d->pw1 ? 1 : 0) | (d->r1l ? 2 : 0) : 0;
-    info->reserved0 = 0;
+    info->u8_staged = d->u8_staged;
     return QPD_OK;
 }
 
@@ -925,31 +931,23 @@ int64_t ensure_pre_rows(qpd_decoder *d, int64_t chunk, int *rc) {
 
 // Launches of one device-buffer decode on stream st (caller: lock held,
 // stream ordered).
-int decode_impl(qpd_decoder *d, const int32_t *d_symbols, int64_t B, uint8_t *d_out, hipStream_t st) {
+// Pre-mode: the root pre-pass on the channel symbols (int32, or uint8 read as
+// they are), then the decode on its rows, chunk by chunk.  fp.in_vec: the
+// symbol rows allow the reader's vector loads (chan_word8).
+template <class In>
+int decode_pre_mode(qpd_decoder *d, qpd::FastPlan fp, const In *d_symbols, int64_t B, uint8_t *d_out, hipStream_t st) {
     int rc = QPD_OK;
-    d->last_engine = QPD_RAN_GPU;
-    if (d->engine != QPD_ENGINE_FAST) {
-        const int64_t groups = (B + d->plan.fpw - 1) / d->plan.fpw;
-        return launch_generic(d, d_symbols, B, d_out, (int)std::min<int64_t>(groups, d->max_waves), st);
-    }
-    qpd::FastPlan fp = d->fplan;
-    fp.in_vec = ((uintptr_t)d_symbols & 15u) == 0 && (fp.N & 3) == 0;
-    if (!d->pre) {
-        fp.in_shift = fp.n;
-        return fast_launch(d, fp, d_symbols, B, d_out, st);
-    }
-    // pre-mode: root pre-pass, then the decode on its rows, chunk by chunk
     const int64_t chunk = ensure_pre_rows(d, std::min<int64_t>(B, d->pre_chunk), &rc);
     if (rc) return rc;
     uint32_t *pre = (uint32_t *)d->pre_buf.p;
     for (int64_t f0 = 0; f0 < B; f0 += chunk) {
         int64_t Bc = std::min<int64_t>(chunk, B - f0);
-        const int32_t *sym = d_symbols + f0 * fp.N;
+        const In *sym = d_symbols + f0 * fp.N;
         fp.in_shift = fp.n;
         const int pgrid = (int)std::min<int64_t>(((Bc << (fp.n - 4)) + 255) / 256, 8192);
         void *pargs[] = {&fp, &sym, &Bc, &pre};
         rc = timed_launch(d, QPD_KC_PRE, st, [&]() -> int {
-            QPD_HIP(hipLaunchKernel(reinterpret_cast<const void *>(&qpd::root_pre_kernel), dim3(pgrid), dim3(256),
+            QPD_HIP(hipLaunchKernel(reinterpret_cast<const void *>(&qpd::root_pre_kernel<In>), dim3(pgrid), dim3(256),
                                     pargs, 0, st));
             QPD_HIP(hipGetLastError());
             return QPD_OK;
@@ -961,8 +959,80 @@ int decode_impl(qpd_decoder *d, const int32_t *d_symbols, int64_t B, uint8_t *d_
     return QPD_OK;
 }
 
+int decode_impl(qpd_decoder *d, const int32_t *d_symbols, int64_t B, uint8_t *d_out, hipStream_t st) {
+    d->last_engine = QPD_RAN_GPU;
+    d->u8_staged = 0;
+    if (d->engine != QPD_ENGINE_FAST) {
+        const int64_t groups = (B + d->plan.fpw - 1) / d->plan.fpw;
+        return launch_generic(d, d_symbols, B, d_out, (int)std::min<int64_t>(groups, d->max_waves), st);
+    }
+    qpd::FastPlan fp = d->fplan;
+    fp.in_vec = ((uintptr_t)d_symbols & 15u) == 0 && (fp.N & 3) == 0;
+    if (!d->pre) {
+        fp.in_shift = fp.n;
+        return fast_launch(d, fp, d_symbols, B, d_out, st);
+    }
+    return decode_pre_mode(d, fp, d_symbols, B, d_out, st);
+}
+
+// int32 staging for `chunk` frames of uint8 input, sized and grown as
+// qpd_mc_decode sizes mc_sym: halved on an allocation failure, the smaller
+// buffer kept from then on.  Returns the frames per chunk.
+int64_t ensure_u8_stage(qpd_decoder *d, int64_t chunk, int *rc) {
+    *rc = QPD_OK;
+    if (d->u8_fell_back) chunk = std::min(chunk, d->u8_cap);
+    if (d->u8_cap >= chunk) return chunk;
+    if (d->u8_sym.p) (void)hipFree(d->u8_sym.p);
+    d->u8_sym.p = nullptr;
+    d->u8_cap = 0;
+    hipError_t e = hipErrorOutOfMemory;
+    const int64_t want = chunk;
+    while (chunk >= 1 && (e = hipMalloc(&d->u8_sym.p, (size_t)chunk * d->N * sizeof(int32_t))) != hipSuccess) {
+        (void)hipGetLastError();
+        d->u8_sym.p = nullptr;
+        chunk /= 2;
+    }
+    if (e != hipSuccess) {
+        *rc = fail(QPD_E_DEVICE, std::string("uint8 staging hipMalloc: ") + hipGetErrorString(e));
+        return 0;
+    }
+    d->u8_fell_back = chunk < want;
+    d->u8_cap = chunk;
+    return chunk;
+}
+
+// uint8 channel symbols (caller: lock held, stream ordered).  Pre-mode reads
+// them as they are (root_pre_kernel<uint8_t>); everything else widens a chunk
+// into the int32 staging buffer on the same stream and runs the int32 launch.
+int decode_u8_impl(qpd_decoder *d, const uint8_t *d_symbols, int64_t B, uint8_t *d_out, hipStream_t st) {
+    if (d->engine == QPD_ENGINE_FAST && d->pre) {
+        d->last_engine = QPD_RAN_GPU;
+        d->u8_staged = 0;
+        qpd::FastPlan fp = d->fplan;
+        fp.in_vec = ((uintptr_t)d_symbols & 7u) == 0;  // N >= 16: every row and half keeps the base's alignment
+        return decode_pre_mode(d, fp, d_symbols, B, d_out, st);
+    }
+    int rc = QPD_OK;
+    // <= 1 GB of int32 symbols per chunk (2^18 frames at N = 1024)
+    const int64_t lim = d->u8_chunk ? d->u8_chunk : std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)d->N * 4));
+    const int64_t chunk = ensure_u8_stage(d, std::min<int64_t>(B, lim), &rc);
+    if (rc) return rc;
+    int32_t *stage = (int32_t *)d->u8_sym.p;
+    for (int64_t f0 = 0; f0 < B; f0 += chunk) {
+        const int64_t Bc = std::min<int64_t>(chunk, B - f0);
+        const int64_t n = Bc * d->N;
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n / 4 + 255) / 256, 8192));
+        hipLaunchKernelGGL(qpd::widen_u8_kernel, dim3(grid), dim3(256), 0, st, d_symbols + f0 * d->N, n, stage);
+        QPD_HIP(hipGetLastError());
+        if ((rc = decode_impl(d, stage, Bc, d_out + f0 * d->out_bits, st))) return rc;
+    }
+    d->u8_staged = 1;
+    return QPD_OK;
+}
+
 int decode_f64_impl(qpd_decoder *d, const double *d_llr, int64_t B, uint8_t *d_out, hipStream_t st) {
     d->last_engine = QPD_RAN_GPU;
+    d->u8_staged = 0;
     const int64_t groups = (B + d->plan.fpw - 1) / d->plan.fpw;
     const int grid = (int)std::min<int64_t>(groups, d->max_waves);
     return launch_generic(d, d_llr, B, d_out, grid, st);
@@ -1074,6 +1144,16 @@ int qpd_decode(qpd_decoder *d, const int32_t *d_symbols, int64_t B, uint8_t *d_o
     return ordered(d, st, [&]() { return decode_impl(d, d_symbols, B, d_out, st); });
 }
 
+int qpd_decode_u8(qpd_decoder *d, const uint8_t *d_symbols, int64_t B, uint8_t *d_out, void *stream) {
+    if (!d) return fail(QPD_E_INVALID, "null decoder");
+    if (d->dom != qpd::DOM_LUT) return fail(QPD_E_INVALID, "this decoder takes float64 LLRs: use qpd_decode_f64");
+    if (B < 0) return fail(QPD_E_INVALID, "negative batch");
+    if (B == 0) return QPD_OK;
+    if (!d_symbols || !d_out) return fail(QPD_E_INVALID, "null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    return ordered(d, st, [&]() { return decode_u8_impl(d, d_symbols, B, d_out, st); });
+}
+
 int qpd_decode_f64(qpd_decoder *d, const double *d_llr, int64_t B, uint8_t *d_out, void *stream) {
     if (!d) return fail(QPD_E_INVALID, "null decoder");
     if (d->dom == qpd::DOM_LUT) return fail(QPD_E_INVALID, "LUT decoders take int32 channel symbols: use qpd_decode");
@@ -1123,6 +1203,7 @@ template <class Eng, class In>
 static int host_engine_run(qpd_decoder *d, Eng *eng, const In *h_in, int64_t B, uint8_t *h_out) {
     std::lock_guard<std::mutex> lk(d->mu);
     d->last_engine = QPD_RAN_HOST;
+    d->u8_staged = 0;
     int32_t flag = 0;
     for (int64_t b = 0; b < B; ++b) flag |= eng->decode(h_in + b * d->N, h_out + b * d->out_bits);
     return flag ? input_error(flag) : QPD_OK;
@@ -1195,6 +1276,16 @@ int qpd_decode_host(qpd_decoder *d, const int32_t *h_symbols, int64_t B, uint8_t
                           [&](const int32_t *in, uint8_t *out, hipStream_t st) { return decode_impl(d, in, B, out, st); });
 }
 
+int qpd_decode_u8_host(qpd_decoder *d, const uint8_t *h_symbols, int64_t B, uint8_t *h_out) {
+    if (!d) return fail(QPD_E_INVALID, "null decoder");
+    if (d->dom != qpd::DOM_LUT) return fail(QPD_E_INVALID, "this decoder takes float64 LLRs: use qpd_decode_f64_host");
+    if (B <= 0) return B == 0 ? QPD_OK : fail(QPD_E_INVALID, "negative batch");
+    if (!h_symbols || !h_out) return fail(QPD_E_INVALID, "null buffer");
+    if (host_engine_takes(d, B)) return host_engine_run(d, d->heng_lut.get(), h_symbols, B, h_out);
+    return host_roundtrip(d, h_symbols, B, h_out,
+                          [&](const uint8_t *in, uint8_t *out, hipStream_t st) { return decode_u8_impl(d, in, B, out, st); });
+}
+
 int qpd_decode_f64_host(qpd_decoder *d, const double *h_llr, int64_t B, uint8_t *h_out) {
     if (!d) return fail(QPD_E_INVALID, "null decoder");
     if (d->dom == qpd::DOM_LUT) return fail(QPD_E_INVALID, "LUT decoders take int32 channel symbols: use qpd_decode_host");
@@ -1243,6 +1334,7 @@ int qpd_mc_decode(qpd_decoder *d, const qpd_mc_channel *ch, uint64_t seed, int64
         // range check); else int32 symbols in a buffer of its own
         const bool fused = d->engine == QPD_ENGINE_FAST && d->pre && ch->q <= d->v;
         d->last_engine = QPD_RAN_GPU;
+        d->u8_staged = 0;
         int64_t chunk;
         if (fused) {
             int r0 = QPD_OK;

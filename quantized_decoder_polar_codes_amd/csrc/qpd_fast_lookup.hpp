@@ -76,6 +76,47 @@ __device__ __forceinline__ uint32_t chan_word8(const int32_t *y, int e0, bool ve
     return w;
 }
 
+// The same from uint8 input (qpd_decode_u8; read by root_pre_kernel only, so v <= 16).
+// `vec` = the input rows are 8-byte aligned: the eight symbols are one 64-bit
+// load, range-checked and packed SWAR.  A byte is out of range when its high
+// nibble is set or its low nibble is >= v: adding 16 - v to the low nibbles
+// carries into bit 4 exactly then (at most 15 + 14: no carry leaves the byte).
+// As for int32, a bad symbol decodes as 0 and raises the error word.
+__device__ __forceinline__ uint32_t chan_word(const uint8_t *y, int e0, int cnt, int v, int32_t *err) {
+    uint32_t w = 0, bad = 0;
+#pragma unroll 1
+    for (int i = 0; i < cnt; ++i) {
+        const uint32_t s = y[e0 + i];
+        bad |= s >= (uint32_t)v;
+        w |= (s >= (uint32_t)v ? 0u : s) << (4 * i);
+    }
+    if (bad) atomicOr(err, 1);
+    return w;
+}
+
+__device__ __forceinline__ uint32_t nib_pack4(uint32_t x) {  // bytes 0-3 of x (each < 16) -> nibbles 0-3
+    const uint32_t t = (x | (x >> 4)) & 0x00FF00FFu;
+    return (t | (t >> 8)) & 0xFFFFu;
+}
+
+__device__ __forceinline__ uint32_t chan_word8(const uint8_t *y, int e0, bool vec, int v, int32_t *err) {
+    if (!vec) return chan_word(y, e0, 8, v, err);
+    const uint2 x = *(const uint2 *)(y + e0);
+    const uint32_t k = (uint32_t)(16 - v) * 0x01010101u;
+    uint32_t lo0 = x.x & 0x0F0F0F0Fu, lo1 = x.y & 0x0F0F0F0Fu;
+    // bits 7:4 of each byte: the high nibble, or the carry of low nibble + 16 - v
+    const uint32_t t0 = (x.x & 0xF0F0F0F0u) | ((lo0 + k) & 0x10101010u);
+    const uint32_t t1 = (x.y & 0xF0F0F0F0u) | ((lo1 + k) & 0x10101010u);
+    if (t0 | t1) {  // rare: clear the bad bytes (nibble != 0 -> bit 4 -> 0x0F)
+        const uint32_t f0 = (((t0 >> 4) & 0x0F0F0F0Fu) + 0x0F0F0F0Fu) & 0x10101010u;
+        const uint32_t f1 = (((t1 >> 4) & 0x0F0F0F0Fu) + 0x0F0F0F0Fu) & 0x10101010u;
+        lo0 &= ~(f0 - (f0 >> 4));
+        lo1 &= ~(f1 - (f1 >> 4));
+        atomicOr(err, 1);
+    }
+    return nib_pack4(lo0) | (nib_pack4(lo1) << 16);
+}
+
 // Word w (8 symbols) of S[d] of the path whose slot is `src`.
 // The first `cnt` channel symbols as one nibble word, a rolled loop: the
 // channel reads of the ops that see the channel only in codes of N <= 8 (the

@@ -1,5 +1,6 @@
 // qpd_fast_pre.hpp -- the fast engine's root pre-pass kernel (pre-mode), launched
-// by qpd_capi.hip before the decode kernels of qpd_fast.hip.
+// by qpd_capi.hip before the decode kernels of qpd_fast.hip, and the widening copy
+// of uint8 channel symbols for the decoders that have no pre-pass (widen_u8_kernel).
 #pragma once
 #include "qpd_fast_switches.hpp"
 
@@ -23,7 +24,8 @@ namespace qpd {
 // The root's f and g tables as bytes in LDS once per block (stage_tab): an
 // element's 8-bit index addresses all three results (f, g with u = 0 at +0,
 // u = 1 at +256) -- one field extract and three ds_read_u8 per element.
-__global__ __launch_bounds__(256) void root_pre_kernel(FastPlan P, const int32_t *__restrict__ in, int64_t B,
+template <class In>
+__global__ __launch_bounds__(256) void root_pre_kernel(FastPlan P, const In *__restrict__ in, int64_t B,
                                                        uint32_t *__restrict__ pre) {
     __shared__ __attribute__((aligned(16))) uint8_t tf[256], tg[512];
     if (threadIdx.x < 64) {  // node 0 (posi 0)
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(256) void root_pre_kernel(FastPlan P, const int32_t
         const int64_t t = t0 < total ? t0 : total - 1;
         const int64_t f = t >> wsh;
         const int w = (int)(t & ((1 << wsh) - 1));
-        const int32_t *y = in + (f << P.n);
+        const In *y = in + (f << P.n);
         const uint32_t a = chan_word8(y, 8 * w, P.in_vec, P.v, P.err);
         const uint32_t b = chan_word8(y, half + 8 * w, P.in_vec, P.v, P.err);
         const uint32_t X = ((a << 4) & 0xF0F0F0F0u) | (b & 0x0F0F0F0Fu);  // byte j: index of element 2j
@@ -59,6 +61,33 @@ __global__ __launch_bounds__(256) void root_pre_kernel(FastPlan P, const int32_t
             row[(2 << wsh) + w] = g1;
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// uint8 channel symbols of everything that is not pre-mode (the generic engine;
+// fast-engine decoders of N < 16, with a special left child of the root or under
+// QPD_NO_PRE): widened into a handle-owned int32 staging buffer, chunk by chunk,
+// for the int32 launch that exists (qpd_capi.hip: decode_u8_impl).  None of
+// these is a hot path -- the generic engine decodes 0.4-0.6 M frames/s, frames
+// of N < 16 are a few bytes -- so their kernels are not templates over the
+// input type: one more copy of each would buy nothing measurable.  The range
+// check stays in the int32 readers.  Four symbols per thread (one 32-bit load,
+// one 128-bit store) where the source is 4-byte aligned, else one.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void widen_u8_kernel(const uint8_t *__restrict__ in, int64_t n,
+                                                       int32_t *__restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int64_t done = 0;
+    if (((uintptr_t)in & 3u) == 0) {
+        const int64_t nq = n >> 2;
+        for (int64_t q = t; q < nq; q += stride) {
+            const uint32_t x = ((const uint32_t *)in)[q];
+            ((int4 *)out)[q] = make_int4((int)(x & 255u), (int)((x >> 8) & 255u), (int)((x >> 16) & 255u), (int)(x >> 24));
+        }
+        done = nq << 2;
+    }
+    for (int64_t i = done + t; i < n; i += stride) out[i] = in[i];
 }
 
 }  // namespace qpd

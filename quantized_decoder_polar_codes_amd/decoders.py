@@ -170,26 +170,33 @@ class _DecoderBase:
     def decode_batch(self, x):
         """Decode B frames.  numpy [B, N] -> numpy uint8 [B, K] (synchronous);
         torch CUDA tensor [B, N] -> torch CUDA uint8 [B, K] on the current stream.
-        (A instead of K for the CRC-aided decoders.)"""
+        (A instead of K for the CRC-aided decoders.)  LUT decoders: uint8 symbols
+        go to the library as they are (qpd_decode_u8 / qpd_decode_u8_host, a
+        quarter of the bytes); any other dtype is converted to int32."""
         torch = _torch()
         lib = _lib.load()
         if torch is not None and isinstance(x, torch.Tensor) and x.is_cuda:
-            want = torch.float64 if self._float_input else torch.int32
+            # uint8 symbols of a LUT decoder go to the library as they are (qpd_decode_u8);
+            # every other dtype (int8 and bool included) is converted to int32 as before
+            u8 = not self._float_input and x.dtype == torch.uint8
+            want = torch.float64 if self._float_input else torch.uint8 if u8 else torch.int32
             xs = x.reshape(-1, self.N).to(want).contiguous()
             B = xs.shape[0]
             out = torch.empty((B, self.out_bits), dtype=torch.uint8, device=xs.device)
             stream = torch.cuda.current_stream(xs.device).cuda_stream
-            fn = lib.qpd_decode_f64 if self._float_input else lib.qpd_decode
+            fn = lib.qpd_decode_f64 if self._float_input else lib.qpd_decode_u8 if u8 else lib.qpd_decode
             _lib.check(fn(self._h, ctypes.c_void_p(xs.data_ptr()), B, ctypes.c_void_p(out.data_ptr()),
                           ctypes.c_void_p(stream)))
             return out
         if torch is not None and isinstance(x, torch.Tensor):
             x = x.numpy()
         a = np.asarray(x)
-        a = np.ascontiguousarray(a.astype(np.float64 if self._float_input else np.int32).reshape(-1, self.N))
+        u8 = not self._float_input and a.dtype == np.uint8
+        want = np.float64 if self._float_input else np.uint8 if u8 else np.int32
+        a = np.ascontiguousarray(a.astype(want, copy=False).reshape(-1, self.N))
         B = a.shape[0]
         out = np.empty((B, self.out_bits), dtype=np.uint8)
-        fn = lib.qpd_decode_f64_host if self._float_input else lib.qpd_decode_host
+        fn = lib.qpd_decode_f64_host if self._float_input else lib.qpd_decode_u8_host if u8 else lib.qpd_decode_host
         _lib.check(fn(self._h, _ptr(a), B, _ptr(out)))
         return out
 
