@@ -45,6 +45,7 @@
 #include <cstdint>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <vector>
 
 namespace {
@@ -334,9 +335,25 @@ struct SCLDec {
     bool fast;
     int L;
     double pm_init = kInf;  // DOUBLE_INF: 1.0/0.0 (LUT kinds, FastSCL), 1e300 (SCLDecoder.h:8 ...)
-    std::vector<std::vector<T>> sym;
-    std::vector<std::vector<uint8_t>> ucap;
+    // Per path and depth d: the symbols of the node on the current descent (N >> d of them) and the
+    // partial sums of the last left (0) and right (1) node finished at that depth.  The reference
+    // keeps an (n + 1) x N array of each per path and copies all of it at every fork; every op writes
+    // a node's block whole, so a fork that copies the blocks' handles leaves each path the same
+    // contents at a cost that does not grow with N (N = 65536: minutes per frame otherwise).
+    template <class X>
+    using Block = std::shared_ptr<std::vector<X>>;
+    struct Path {
+        std::vector<Block<T>> S;
+        std::vector<Block<uint8_t>> U;  // [2 * d + (node & 1)]
+    };
+    std::vector<Path> path;
     std::vector<double> pm;
+    const T *S(int i, int d) const { return path[i].S[d]->data(); }
+    const uint8_t *U(int i, int d, int node) const { return path[i].U[2 * d + (node & 1)]->data(); }
+    T *new_S(int i, int d) { return (path[i].S[d] = std::make_shared<std::vector<T>>(c.N >> d))->data(); }
+    uint8_t *new_U(int i, int d, int node) {
+        return (path[i].U[2 * d + (node & 1)] = std::make_shared<std::vector<uint8_t>>(c.N >> d))->data();
+    }
 
     CaSpec ca;  // ca.A > 0: CRC-aided output of A bits
 
@@ -355,14 +372,9 @@ struct SCLDec {
         }
     }
     void permute(const std::vector<int> &parent) {
-        std::vector<std::vector<T>> s2(L);
-        std::vector<std::vector<uint8_t>> u2(L);
-        for (int i = 0; i < L; ++i) {
-            s2[i] = sym[parent[i]];
-            u2[i] = ucap[parent[i]];
-        }
-        sym.swap(s2);
-        ucap.swap(u2);
+        std::vector<Path> p2(L);
+        for (int i = 0; i < L; ++i) p2[i] = path[parent[i]];
+        path.swap(p2);
     }
 
     // Leaf k from a node at depth n-1 (left :91-145, right :166-221).
@@ -372,14 +384,14 @@ struct SCLDec {
         const int temp = N >> d, half = temp / 2;
         std::vector<double> dm(L);
         for (int i = 0; i < L; ++i) {
-            const T *p = &sym[i][d * N + temp * node];
-            T s = right ? dom.g(posi, 0, ucap[i][(d + 1) * N + half * (2 * node)], p[0], p[half])
+            const T *p = S(i, d);
+            T s = right ? dom.g(posi, 0, U(i, d + 1, 2 * node)[0], p[0], p[half])
                         : dom.f(posi, 0, p[0], p[half]);
             dm[i] = dom.llr(n - 1, k, s);
         }
         if (c.frozen[k] == 1) {
             for (int i = 0; i < L; ++i) {
-                ucap[i][n * N + k] = 0;
+                new_U(i, n, k)[0] = 0;
                 pm[i] += std::fabs(dm[i]) * (double)(dm[i] < 0);
             }
             return;
@@ -397,7 +409,7 @@ struct SCLDec {
         permute(parent);
         for (int i = 0; i < L; ++i) {
             uint8_t b = dec[parent[i]];
-            ucap[i][n * N + k] = upper[i] ? (uint8_t)(1 - b) : b;
+            new_U(i, n, k)[0] = upper[i] ? (uint8_t)(1 - b) : b;
         }
     }
 
@@ -411,12 +423,11 @@ struct SCLDec {
         const int t = c.type(posi);
         if (!fast || t < 0 || t > 2) return false;
         const int temp = N >> d;
-        const int off = d * N + temp * node;
         if (t == 0) {  // R0, :83-96
             for (int i = 0; i < L; ++i) {
-                std::memset(&ucap[i][off], 0, temp);
+                new_U(i, d, node);  // zeros
                 for (int j = 0; j < temp; ++j) {
-                    double l = dom.llr(d - 1, temp * node + j, sym[i][off + j]);
+                    double l = dom.llr(d - 1, temp * node + j, S(i, d)[j]);
                     pm[i] += (float)(l < 0) * std::fabs(l);
                 }
             }
@@ -427,7 +438,7 @@ struct SCLDec {
             std::vector<std::vector<int>> order(L);
             for (int i = 0; i < L; ++i) {
                 for (int j = 0; j < temp; ++j) {
-                    double l = dom.llr(d - 1, temp * node + j, sym[i][off + j]);
+                    double l = dom.llr(d - 1, temp * node + j, S(i, d)[j]);
                     dec[i][j] = (uint8_t)(l < 0);
                     mag[i][j] = std::fabs(l);
                 }
@@ -461,7 +472,7 @@ struct SCLDec {
                 mag.swap(mag2);
                 order.swap(order2);
             }
-            for (int i = 0; i < L; ++i) std::memcpy(&ucap[i][off], dec[i].data(), temp);
+            for (int i = 0; i < L; ++i) std::memcpy(new_U(i, d, node), dec[i].data(), temp);
         } else {  // REP, :169-213
             std::vector<double> pm2(2 * L);
             for (int i = 0; i < L; ++i) {
@@ -470,7 +481,7 @@ struct SCLDec {
             }
             for (int i = 0; i < L; ++i) {
                 for (int j = 0; j < temp; ++j) {
-                    double l = dom.llr(d - 1, temp * node + j, sym[i][off + j]);
+                    double l = dom.llr(d - 1, temp * node + j, S(i, d)[j]);
                     pm2[i] += (double)(l < 0) * std::fabs(l);
                     pm2[i + L] += (double)(l >= 0) * std::fabs(l);
                 }
@@ -479,7 +490,7 @@ struct SCLDec {
             std::vector<bool> upper;
             select(pm2, parent, upper);
             permute(parent);
-            for (int i = 0; i < L; ++i) std::memset(&ucap[i][off], upper[i] ? 1 : 0, temp);
+            for (int i = 0; i < L; ++i) std::memset(new_U(i, d, node), upper[i] ? 1 : 0, temp);
         }
         return true;
     }
@@ -490,13 +501,12 @@ struct SCLDec {
         const int posi = (1 << d) + node - 1;
         const int temp = N >> d, half = temp / 2;
         const int l = 2 * node, r = 2 * node + 1;
-        const int off = d * N + temp * node;
         // f (:83-90 / :223-230)
         if (d + 1 < n) {
             for (int i = 0; i < L; ++i) {
-                T *s = sym[i].data();
-                for (int j = 0; j < half; ++j)
-                    s[(d + 1) * N + half * l + j] = dom.f(posi, j, s[off + j], s[off + half + j]);
+                const T *s = S(i, d);
+                T *o = new_S(i, d + 1);
+                for (int j = 0; j < half; ++j) o[j] = dom.f(posi, j, s[j], s[half + j]);
             }
             visit(d + 1, l);
         } else {
@@ -505,40 +515,44 @@ struct SCLDec {
         // g (:157-165 / :297-305)
         if (d + 1 < n) {
             for (int i = 0; i < L; ++i) {
-                T *s = sym[i].data();
-                const uint8_t *ul = &ucap[i][(d + 1) * N + half * l];
-                for (int j = 0; j < half; ++j)
-                    s[(d + 1) * N + half * r + j] = dom.g(posi, j, ul[j], s[off + j], s[off + half + j]);
+                const T *s = S(i, d);
+                const uint8_t *ul = U(i, d + 1, l);
+                T *o = new_S(i, d + 1);
+                for (int j = 0; j < half; ++j) o[j] = dom.g(posi, j, ul[j], s[j], s[half + j]);
             }
             visit(d + 1, r);
         } else {
             leaf(posi, d, node, r, true);
         }
         // combine (:226-241 / :366-384)
-        for (int i = 0; i < L; ++i)
-            combine(&ucap[i][off], &ucap[i][(d + 1) * N + half * l], &ucap[i][(d + 1) * N + half * r], half);
+        for (int i = 0; i < L; ++i) {
+            const Block<uint8_t> ul = path[i].U[2 * (d + 1)], ur = path[i].U[2 * (d + 1) + 1];
+            combine(new_U(i, d, node), ul->data(), ur->data(), half);
+        }
     }
 
     template <class In>
     int run(const In *y, uint8_t *out) {
         const int N = c.N, n = c.n;
         if (fast && c.type(0) >= 0 && c.type(0) <= 2) return -2;  // reference UB (root special)
-        sym.assign(L, std::vector<T>((n + 1) * N));
-        ucap.assign(L, std::vector<uint8_t>((n + 1) * N));
+        path.assign(L, Path{std::vector<Block<T>>(n + 1), std::vector<Block<uint8_t>>(2 * (n + 1))});
         pm.assign(L, pm_init);
         pm[0] = 0;
-        for (int i = 0; i < L; ++i)
-            for (int k = 0; k < N; ++k) sym[i][k] = (T)y[k];
+        for (int i = 0; i < L; ++i) {
+            T *s = new_S(i, 0);
+            for (int k = 0; k < N; ++k) s[k] = (T)y[k];
+        }
         visit(0, 0);
         if (dom.bad()) return -4;
         for (double p : pm)
             if (std::isnan(p)) return -4;  // NaN keys: std::sort's order is undefined
         if (ca.A > 0) {
-            // decoded info bits of a path: ucap[n] (SCL, :268-275) or the re-encoded
-            // root partial sums (FastSCL, :338-355)
-            auto info_of = [&](int path) {
-                std::vector<uint8_t> x(ucap[path].begin() + (fast ? 0 : n * N), ucap[path].begin() + (fast ? N : (n + 1) * N));
-                if (fast) reencode(x, N);
+            // decoded info bits of a path: the leaf decisions (SCL, :268-275) or the re-encoded root
+            // partial sums (FastSCL, :338-355) -- the same bits, the combines being the polar transform
+            // and the transform its own inverse
+            auto info_of = [&](int pth) {
+                std::vector<uint8_t> x(U(pth, 0, 0), U(pth, 0, 0) + N);
+                reencode(x, N);
                 std::vector<uint8_t> info;
                 for (int k = 0; k < N; ++k)
                     if (c.frozen[k] == 0) info.push_back(x[k]);
@@ -566,13 +580,9 @@ struct SCLDec {
             return 0;
         }
         int best = first_argmin(pm);  // H6
-        if (!fast) {
-            emit_info(c, &ucap[best][n * N], out);  // :244-252
-        } else {
-            std::vector<uint8_t> x(ucap[best].begin(), ucap[best].begin() + N);  // :387-406
-            reencode(x, N);
-            emit_info(c, x.data(), out);
-        }
+        std::vector<uint8_t> x(U(best, 0, 0), U(best, 0, 0) + N);  // :244-252 (the leaf decisions) / :387-406
+        reencode(x, N);
+        emit_info(c, x.data(), out);
         return 0;
     }
 };

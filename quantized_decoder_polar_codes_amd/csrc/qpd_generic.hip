@@ -223,16 +223,24 @@ struct PtrW<kMaxLWide> {
     static constexpr int B = 5;
 };
 
+// Depth d's field.  The shift is taken modulo the word's width (what the shift instruction does with
+// its operand anyway): in 64 bits depth 16, the leaf level of N = 65536, shares nibble 0 with depth 0,
+// whose field no op uses -- the root reads the channel and writes R[0], neither through a pointer.
+template <int ML>
+__device__ __forceinline__ int gp_shift(int d) {
+    return (PtrW<ML>::B * d) & (int)(8 * sizeof(typename PtrW<ML>::T) - 1);
+}
+
 template <int ML>
 __device__ __forceinline__ int gp_get(typename PtrW<ML>::T p, int d) {
-    return (int)(p >> (PtrW<ML>::B * d)) & ((1 << PtrW<ML>::B) - 1);
+    return (int)(p >> gp_shift<ML>(d)) & ((1 << PtrW<ML>::B) - 1);
 }
 
 template <int ML>
 __device__ __forceinline__ typename PtrW<ML>::T gp_set(typename PtrW<ML>::T p, int d, int v) {
     using T = typename PtrW<ML>::T;
-    const T m = (T)((1u << PtrW<ML>::B) - 1u) << (PtrW<ML>::B * d);
-    return (p & ~m) | ((T)(unsigned)v << (PtrW<ML>::B * d));
+    const T m = (T)((1u << PtrW<ML>::B) - 1u) << gp_shift<ML>(d);
+    return (p & ~m) | ((T)(unsigned)v << gp_shift<ML>(d));
 }
 
 template <int ML>

@@ -62,7 +62,7 @@ struct MOp {
     int32_t u_row;    // G/COMB: U[d+1]; LEAF_R: U[n]
     int32_t r_row;    // COMB: R[d+1]; F/G with MF_FF: S[d+2]
     int32_t sh_src;   // 4*d: ps field of S[d]
-    int32_t sh_u;     // G/COMB: 4*(d+1); LEAF_R: 4*n
+    int32_t sh_u;     // G/COMB: 4*(d+1); LEAF_R: 4*n (depth 16: nibble 0, u_field in qpd_plan.hpp)
     int32_t sh_dst;   // F/G: 4*(d+1) (ps); COMB/special/BOT3 left child: 4*d (pu); LEAF_L: 4*n (pu)
     int32_t tab;      // F/LEAF_L: posi*32; G/LEAF_R: posi*64; BOT3: posi of the subtree root; R1: r1_rank offset
     int32_t vrow;     // LEAF: ((n-1)*N + k)*v; special: (d-1)*N + temp*node; BOT3: ((n-1)*N + 8*node)*v

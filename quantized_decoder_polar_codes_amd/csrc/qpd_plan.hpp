@@ -202,6 +202,11 @@ inline void r1_rank_table(std::vector<uint16_t> &tab, const double *vcl, int N, 
     }
 }
 
+// The U-row pointer field of depth dd (1 .. n): nibble dd of the path's U word, and for dd = 16 (the
+// leaf level of N = 65536) nibble 0, which no other U row uses -- the root's result goes to R[0]
+// (MF_TO_R: no pointer) and no op reads U[0].  4 * 16 would be a shift by the word's whole width.
+inline int u_field(int dd) { return 4 * (dd & 15); }
+
 inline void fast_ops(std::vector<qpd::MOp> &out, const FastLayout &Ly, const PlanSwitches &sw, int kind, int N, int n, int v,
                      const int32_t *frozen, const int32_t *node_type, const double *vcl, std::vector<uint16_t> &r1tab, int d,
                      int node) {
@@ -369,11 +374,11 @@ inline void fast_ops(std::vector<qpd::MOp> &out, const FastLayout &Ly, const Pla
             m.cnt = frozen[k] == 1;
             m.dst_row = side ? Ly.R[n] : Ly.U[n];
             if (Ly.lds(n)) m.flags |= MF_DST_LDS;
-            m.sh_dst = 4 * n;
+            m.sh_dst = u_field(n);
             if (side) {
                 m.u_row = Ly.U[n];
                 if (Ly.lds(n)) m.flags |= MF_U_LDS;
-                m.sh_u = 4 * n;
+                m.sh_u = u_field(n);
                 m.tab = posi * 64;
             } else {
                 m.tab = posi * 32;
@@ -387,7 +392,7 @@ inline void fast_ops(std::vector<qpd::MOp> &out, const FastLayout &Ly, const Pla
     m.u_row = Ly.U[d + 1];
     m.r_row = Ly.R[d + 1];
     if (Ly.lds(d + 1)) m.flags |= MF_U_LDS | MF_R_LDS;
-    m.sh_u = 4 * (d + 1);
+    m.sh_u = u_field(d + 1);
     finish_node(m);
     out.push_back(m);
 }
@@ -432,6 +437,12 @@ inline void fuse_descent(std::vector<qpd::MOp> &ops) {
 // reads that row and its left sibling's U[n-4]; the BOT3 computes that
 // combine from its result in registers and writes the COMB's destination, so
 // R[n-4] is neither stored nor loaded and the COMB op goes.  SCL-LUT only.
+// pad1 of an MF_BC2 op: the folded combine's U pointer field, its destination's, and its destination
+// row in the 16 bits above them -- read back with `pad1 >> 16` on the int32_t, so rows below 32768 only
+inline int32_t bc2_pack(int sh_u, int sh_dst, int dst_row) {
+    return (int32_t)((uint32_t)sh_u | ((uint32_t)sh_dst << 8) | ((uint32_t)dst_row << 16));
+}
+
 inline void fold_combine(std::vector<qpd::MOp> &ops) {
     using namespace qpd;
     std::vector<MOp> out;
@@ -446,7 +457,7 @@ inline void fold_combine(std::vector<qpd::MOp> &ops) {
                 a.flags |= MF_BC2 | ((b.flags & MF_U_LDS) ? MF_BC2_ULDS : 0) | ((b.flags & MF_DST_LDS) ? MF_BC2_DLDS : 0) |
                            ((b.flags & MF_TO_R) ? MF_BC2_TOR : 0);
                 a.r_row = b.u_row;
-                a.pad1 = b.sh_u | (b.sh_dst << 8) | (b.dst_row << 16);
+                a.pad1 = bc2_pack(b.sh_u, b.sh_dst, b.dst_row);
                 out.push_back(a);
                 ++i;
                 continue;
@@ -708,7 +719,7 @@ inline bool plan_prefix(const std::vector<qpd::MOp> &ops, const FastOwner &own, 
         live_runs(live, own, [&](int sp, int r, int cnt, int slot, int dd) {
             MOp x = blank_op(OP_EXPORT);
             x.flags = (sp ? MF_SRC_LDS : 0) | (slot == 1 ? MF_VIA_PS : slot == 2 ? MF_VIA_PU : 0);
-            x.sh_src = 4 * dd;
+            x.sh_src = slot == 2 ? u_field(dd) : 4 * dd;
             x.src_row = r;
             x.dst_row = w;
             x.cnt = cnt;

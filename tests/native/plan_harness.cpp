@@ -50,6 +50,53 @@ bool same_plan(const FastHostPlan &a, const FastHostPlan &b) {
            x.lds_end == y.lds_end && x.pre == y.pre && x.bfuse == y.bfuse && x.ns == y.ns && x.botx == y.botx;
 }
 
+// The kernels' unpack expressions of the values the plan packs into part of a
+// record word, each as the kernel writes it (on the int32_t field of the record).
+//   MF_BC2's pad1, the end of bot3_op (qpd_fast_bot.hpp): `const int e = op.pad1;` then
+//   `pfield(st[s].U(), e & 255)`, `M[s].st(op.flags & MF_BC2_DLDS, e >> 16, lane, res)` and
+//   `pset(st[s].U(), (e >> 8) & 255, gl)`
+inline int bc2_u_field(int32_t e) { return e & 255; }
+inline int bc2_dst_field(int32_t e) { return (e >> 8) & 255; }
+inline int bc2_dst_row(int32_t e) { return e >> 16; }
+//   MF_R1_RK's rank and sign words, rank_of in r1_prep (qpd_fast_special.hpp):
+//   `RK = ((uint64_t)(uint32_t)op.tab2 << 32) | (uint32_t)op.r_row` and
+//   `((uint32_t)(RK >> (4 * sym)) & 15u) << 1 | (((uint32_t)op.pad1 >> sym) & 1u)`
+inline uint32_t r1rk_entry(const qpd::MOp &m, int sym) {
+    const uint64_t RK = ((uint64_t)(uint32_t)m.tab2 << 32) | (uint32_t)m.r_row;
+    return ((uint32_t)(RK >> (4 * sym)) & 15u) << 1 | (((uint32_t)m.pad1 >> sym) & 1u);
+}
+//   a pointer field, pfield / pset (qpd_fast_lookup.hpp): `(p >> sh) & 15u` and `15ull << sh` on the
+//   path's 64-bit pointer word (PathT, qpd_fast_select.hpp: uint64_t ps, pu; one word of them on a PW1
+//   plan), so a field is a whole nibble of that word
+inline bool field_in_word(int sh) { return sh >= 0 && sh % 4 == 0 && sh + 4 <= 64; }
+
+// Every packed value of op m comes back from the kernel's unpack expression as the value the plan
+// meant: the pointer fields (pointer_fields presents an MF_BC2 op's two packed ones unpacked, by the
+// expressions above), an MF_BC2 op's result row `bc2_row` (the caller's: what the layout says the
+// folded combine writes), an MF_R1_RK op's ranks and signs (`r1`: the node's rank keys, or null).
+// The empty string, or what does not round-trip.
+std::string check_packed(const qpd::MOp &m, int bc2_row, const uint16_t *r1, int v) {
+    using namespace qpd;
+    std::string bad;
+    MOp t = m;
+    int bc_u = 0, bc_dst = 0;
+    pointer_fields(t, bc_u, bc_dst, [&](int, int &sh) {
+        if (bad.empty() && !field_in_word(sh)) bad = "pointer field at shift " + std::to_string(sh) + " is not a nibble of a 64-bit word";
+    });
+    if (!bad.empty()) return bad;
+    if (m.type == OP_BOT3 && (m.flags & MF_BC2)) {
+        if (bc_u != bc2_u_field(m.pad1) || bc_dst != bc2_dst_field(m.pad1)) return "pointer_fields and the kernel unpack pad1 differently";
+        if (bc2_dst_row(m.pad1) != bc2_row)
+            return "pad1 >> 16 gives row " + std::to_string(bc2_dst_row(m.pad1)) + ", the plan packed row " + std::to_string(bc2_row);
+    }
+    if ((m.flags & MF_R1_RK) && r1)
+        for (int sy = 0; sy < v; ++sy)
+            if (r1rk_entry(m, sy) != r1[sy])
+                return "rank key of symbol " + std::to_string(sy) + " unpacks to " + std::to_string(r1rk_entry(m, sy)) + ", the rank table has " +
+                       std::to_string(r1[sy]);
+    return bad;
+}
+
 void check_plan(const qpd_config &c, int n, const Schedule &s, const FastHostPlan &P, Fail &fail) {
     using namespace qpd;
     const int N = c.N;
@@ -78,13 +125,18 @@ void check_plan(const qpd_config &c, int n, const Schedule &s, const FastHostPla
             // the unservable f / g shape
             if ((m.type == OP_F || m.type == OP_G) && (m.flags & MF_SRC_LDS) && !(m.flags & MF_DST_LDS))
                 fail(names[li], i, m, "f/g op reads LDS rows and writes slab rows");
-            // one pointer word: every field the op uses is a nibble position of it
-            if (P.pw1) {
-                MOp t = m;
-                int bc_u = 0, bc_dst = 0;
-                pointer_fields(t, bc_u, bc_dst, [&](int, int &sh) {
-                    if (sh < 0 || sh >= 64 || sh % 4) fail(names[li], i, m, "pointer field " + std::to_string(sh) + " outside one word");
-                });
+            // packed values: every pointer field a nibble of the path's word (one word or two), and what
+            // the kernel unpacks is what the plan packed.  An MF_BC2 op writes the row of its grandparent
+            // (depth d - 2): R if that is a right child, else U, in LDS where the layout has that depth
+            {
+                const int gd = m.d - 2;
+                const bool bc2 = m.type == OP_BOT3 && (m.flags & MF_BC2);
+                if (bc2 && (gd < 0 || ((m.flags & MF_BC2_DLDS) != 0) != P.layout.lds(gd)))
+                    fail(names[li], i, m, "MF_BC2: the result row's space is not the layout's of depth d - 2");
+                const int row = !bc2 || gd < 0 ? 0 : (m.flags & MF_BC2_TOR) ? P.layout.R[gd] : P.layout.U[gd];
+                const bool own_tab = m.type == OP_R1 && !(m.flags & MF_SFG) && m.tab >= 0 && (size_t)m.tab + c.v <= P.r1tab.size();
+                const std::string bad = check_packed(m, row, own_tab ? P.r1tab.data() + m.tab : nullptr, c.v);
+                if (!bad.empty()) fail(names[li], i, m, bad);
             }
             // prefix records
             if (m.type == OP_IMPORT && (m.flags & MF_XBUF)) {
@@ -119,6 +171,32 @@ void check_plan(const qpd_config &c, int n, const Schedule &s, const FastHostPla
 }  // namespace
 
 extern "C" int ph_switches_size(void) { return (int)sizeof(qpd_plan::PlanSwitches); }
+
+// Self-test of check_packed: plans cfg, takes a copy of its first MF_BC2 record, packs `dst_row`
+// into the copy as fold_combine does (bc2_pack) and runs the check on it.  0: the copy round-trips;
+// 1: the check fails (msg); -1: the plan has no MF_BC2 op; -2: no plan.
+extern "C" int ph_pack_selftest(const qpd_config *cfg, const qpd_plan::PlanSwitches *sw, int dst_row, char *msg, int msg_len) {
+    int fam = 0, dom = 0, n = 0;
+    msg[0] = 0;
+    if (!qpd_sched::family_of(cfg->kind, &fam, &dom) || dom != qpd::DOM_LUT) return -2;
+    qpd_config c = *cfg;
+    c.kind = fam;
+    while ((1 << n) < c.N) ++n;
+    Schedule s;
+    qpd_sched::visit(s, fam, c.N, n, c.frozen_bits, nullptr, 0, 0);
+    FastHostPlan P;
+    std::string err;
+    if (plan_fast(c, n, c.L, s, *sw, P, err)) return -2;
+    for (const MOp &m : P.ops)
+        if (m.type == qpd::OP_BOT3 && (m.flags & qpd::MF_BC2)) {
+            MOp t = m;
+            t.pad1 = bc2_pack(bc2_u_field(m.pad1), bc2_dst_field(m.pad1), dst_row);
+            const std::string bad = check_packed(t, dst_row, nullptr, c.v);
+            snprintf(msg, msg_len, "%s", bad.c_str());
+            return bad.empty() ? 0 : 1;
+        }
+    return -1;
+}
 
 // 0: planned and every invariant holds; 1: an invariant fails; < 0: plan_fast's
 // refusal (its code); -100: not a fast-engine configuration.  msg: the failure

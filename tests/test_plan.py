@@ -5,11 +5,13 @@ wrong row there is silent corruption or a memory fault, not a failed assert.
 tests/native/plan_harness.cpp (g++, no HIP) plans a configuration the way
 qpd_create does and verifies in C++ what the kernels rely on: rows inside
 their space and in slots the layout kept, the R1 argsort scratch, the LDS
-size and budget, the one-word pointer fields, the prefix stages' records, the
+size and budget, the pointer fields and every other value packed into part of a
+record word (read back by the kernels' own expressions), the prefix stages' records, the
 f / g shape plan_fast refuses, and that planning twice gives the same bytes.
 
 The sweep: every LUT kind; the 5G PW codes at N = 8 .. 1024 with a low, half
-and high rate, N = 2048 and 4096 with the BEC construction; L = 1 (SC kinds) or
+and high rate, N = 2048 and 4096 with the BEC construction (N = 8192, 16384 and 65536
+under a reduced switch list); L = 1 (SC kinds) or
 2, 4, 8, 12, 16; tie-heavy random tables and the MinDistortion tables of the
 committed goldens; each switch on its own and the LDS budgets the GPU tests use.
 Beside that point of the input space (v = 16, nested reliability orders): the
@@ -212,6 +214,76 @@ def test_plan_invariants_long_codes(kind, N, K, harness):
 
     p = LU.random_luts(N, 16, seed=3 * N + K, distinct_mags=3)
     sweep(harness, kind, N, K, p, list_sizes(kind), SWEEP)
+
+
+@pytest.fixture(scope="module")
+def long_tables():
+    """Tie-heavy random tables per N, made once for the four kinds."""
+    from quantized_decoder_polar_codes_amd import lut as LU
+
+    made = {}
+
+    def get(N):
+        if N not in made:
+            made[N] = LU.random_luts(N, 16, seed=3 * N + 1, distinct_mags=3)
+        return made[N]
+
+    return get
+
+
+# default, the smallest and the largest LDS budget (the whole tree in the slab / every depth the budget
+# admits in LDS), and the switches that change which fields and rows a record packs
+LONG_SWEEP = [{}, {"lds_budget": 256}, {"lds_budget": 65536}, {"no_pw1": True}, {"no_bc2": True}, {"no_trim": True},
+              {"no_pfx": True}]
+
+
+@pytest.mark.parametrize("N", [8192, 16384, 65536])
+@pytest.mark.parametrize("kind", KINDS)
+def test_plan_invariants_very_long_codes(kind, N, harness, long_tables):
+    """The four deepest trees qpd_create accepts (n = 13, 14, 16; 4096 and 32768 differ from their neighbours
+    in no field width) at a low, a half and a high rate: row numbers beside the 16 bits MF_BC2 packs them
+    into, pointer fields at the last nibbles of the word (the leaf level of n = 16 takes nibble 0: u_field),
+    R1 nodes of thousands of elements.  The only refusal is the W16 one (sweep asserts it).
+
+    Measured on one core, N = 8192 / 16384 / 65536: random_luts 0.1 / 0.5 / 0.9 s, the BEC construction and
+    identify_nodes below 0.02 s, from_packed(create=False) 1 ms, ph_check 0.03 / 0.05 / 0.15 s per switch
+    setting; the whole test (12 cases) 29 s, its slowest case (SCL-LUT, N = 65536) 8 s."""
+    p = long_tables(N)
+    for K in rates(N):
+        fm, nt = code(N, K)
+        big = max(r1_sizes(nt, N))
+        if K == 3 * N // 4:
+            assert big >= N // 4  # R1 nodes far above 32 elements (r1_large, the slab's H / K / I rows)
+        r = sweep(harness, kind, N, K, p, [8, 16] if "SCL" in kind else [1], LONG_SWEEP)
+        assert r is not None
+        if kind == "FastSCL-LUT" and big > 32:  # L = 16 is refused under every setting, L = 8 planned
+            assert r[0] == {(16, tuple(kw.items())) for kw in LONG_SWEEP}
+        else:
+            assert not r[0]
+
+
+def test_packed_fields_round_trip(harness):
+    """check_packed of the harness notices a row that does not fit the 16 bits above MF_BC2's pointer
+    fields: a copy of a planned record with row 40000 packed into it reads back negative."""
+    from quantized_decoder_polar_codes_amd import decoders as D
+    from quantized_decoder_polar_codes_amd import lut as LU
+
+    N, K = 1024, 512
+    fm, nt = code(N, K)
+    dec = D.from_packed("SCL-LUT", LU.random_luts(N, 16, seed=7, distinct_mags=3), K, fm, L=8, create=False)
+    harness.ph_pack_selftest.argtypes = [ctypes.c_void_p, ctypes.POINTER(Switches), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+    harness.ph_pack_selftest.restype = ctypes.c_int
+
+    def selftest(row, **kw):
+        msg = ctypes.create_string_buffer(256)
+        sw = switches(**kw)
+        return harness.ph_pack_selftest(ctypes.byref(dec._cfg), ctypes.byref(sw), row, msg, len(msg)), msg.value.decode()
+
+    for kw in ({}, {"no_pw1": True}):
+        assert selftest(0, **kw) == (0, "") and selftest(123, **kw) == (0, "") and selftest(32767, **kw) == (0, "")
+        assert selftest(40000, **kw) == (1, "pad1 >> 16 gives row -25536, the plan packed row 40000")
+        assert selftest(32768, **kw)[0] == 1
+    assert selftest(0, no_bc2=True)[0] == -1  # no MF_BC2 record to copy
 
 
 @pytest.mark.parametrize("golden", ["sclut_n128_k32_mindist", "scllut_n1024_k512_l8_mindist", "fastscllut_n1024_k512_l8_mindist"])
