@@ -1,0 +1,247 @@
+// qpd_capi_decode.hpp -- the launches of one device-buffer decode on a stream
+// (caller: lock held, stream ordered -- qpd_decoder.hpp: ordered): int32,
+// uint8 and f64 input, the generic engine, the fast engine with its root
+// pre-pass and frozen-prefix stages.  Host code.
+#pragma once
+#include "qpd_capi_build.hpp"
+#include "qpd_decoder.hpp"
+#include "qpd_fast_pre.hpp"
+
+namespace {
+
+// The stage whose records an import op reads, from the planner's encoding in op.node
+// (plan_prefix in qpd_plan.hpp; tests/test_plan.py pins it): 1 = stage 1, 2 = stage 2,
+// 3 = stage 1b -- not the stages' order in qpd_decoder::pfx.
+int import_stage(const qpd::MOp &m) { return m.node == 3 ? 1 : m.node == 2 ? 2 : 0; }
+
+// Point the import ops of a prefix-split schedule at the stage buffers, on the launch
+// stream, when a buffer moved.
+int patch_imports(qpd_decoder *d, hipStream_t st) {
+    bool moved = false;
+    for (const auto &sg : d->pfx) moved = moved || sg.patched != sg.buf.p;
+    if (!moved) return QPD_OK;
+    auto patch = [&](std::vector<qpd::MOp> &v) {
+        for (qpd::MOp &m : v)
+            if (m.type == qpd::OP_IMPORT && (m.flags & qpd::MF_XBUF)) {
+                const uint64_t a = (uint64_t)(uintptr_t)d->pfx[import_stage(m)].buf.p;
+                m.u_row = (int32_t)(uint32_t)a;
+                m.r_row = (int32_t)(uint32_t)(a >> 32);
+            }
+    };
+    patch(d->pfx_ops_host);
+    patch(d->main_ops_host);
+    QPD_HIP(hipMemcpyAsync(d->pfx_mops.p, d->pfx_ops_host.data(), d->pfx_ops_host.size() * sizeof(qpd::MOp),
+                           hipMemcpyHostToDevice, st));
+    QPD_HIP(hipMemcpyAsync(d->mops.p, d->main_ops_host.data(), d->main_ops_host.size() * sizeof(qpd::MOp),
+                           hipMemcpyHostToDevice, st));
+    for (auto &sg : d->pfx) sg.patched = sg.buf.p;
+    return QPD_OK;
+}
+
+// A stage's record buffer for Bc frames (rounded up to whole 64-frame groups), grown on demand.
+// (No smaller size on an allocation failure, unlike the chunk buffers: ADVICE.md.)
+int ensure_records(DeviceBuf &b, size_t &cap, int64_t Bc, int rec, int paths) {
+    const size_t need = (size_t)((Bc + 63) / 64 * 64) * (size_t)rec * paths * sizeof(uint32_t);
+    if (cap >= need) return QPD_OK;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    cap = 0;
+    const hipError_t e = hipMalloc(&b.p, need);
+    if (e != hipSuccess) return fail(QPD_E_DEVICE, std::string("prefix records hipMalloc: ") + hipGetErrorString(e));
+    cap = need;
+    return QPD_OK;
+}
+
+template <class In>
+int launch_generic(qpd_decoder *d, const In *in, int64_t B, uint8_t *out, int grid, hipStream_t st) {
+    const void *kfn = generic_kernel(d->kind, d->dom, d->L > qpd::kMaxL);
+    if (!kfn) return fail(QPD_E_INVALID, "bad kind");
+    qpd::DevPlan P = d->plan;
+    P.task_base = d->task_base;
+    const In *in_arg = in;
+    void *args[] = {&P, &in_arg, &B, &out};
+    const int rc = timed_launch(d, QPD_KC_DECODE, st, [&]() -> int {
+        QPD_HIP(hipLaunchKernel(kfn, dim3(grid), dim3(64), args, 0, st));
+        QPD_HIP(hipGetLastError());
+        return QPD_OK;
+    });
+    if (!rc) d->task_base += (uint32_t)((B + d->plan.fpw - 1) / d->plan.fpw);  // takes of this launch (wave_take)
+    return rc;
+}
+
+// One fast-engine decode launch over Bc frames whose rows start at `in`
+// (channel symbols, in_shift = n; or pre-pass rows, in_shift = n - 2).
+int fast_launch(qpd_decoder *d, qpd::FastPlan fp, const int32_t *in, int64_t Bc, uint8_t *out, hipStream_t st,
+                bool prefix = false) {
+    const int sets = prefix ? d->pfx_sets : d->sets;
+    const int64_t tw = (int64_t)fp.fpw * sets;  // frames per wave task
+    const void *kfn = prefix ? prefix_kernel(d->kind, sets, d->pw1) : fast_kernel(d->kind, d->sets, d->l8, d->r1l, d->pw1, d->w16);
+    if (!kfn) return fail(QPD_E_INVALID, "bad kind");
+    const int64_t fgroups = (Bc + tw - 1) / tw;
+    int fgrid = (int)std::min<int64_t>(fgroups, d->max_waves);
+    if (!QPD_DYN) {
+        // even out the rounds of the grid-stride loop (no partial last round)
+        const int64_t rounds = (fgroups + fgrid - 1) / fgrid;
+        fgrid = (int)((fgroups + rounds - 1) / rounds);
+    }
+    const qpd::MOp *ops_arg = fp.ops;
+    fp.task_base = d->task_base;
+    void *args[] = {&fp, &in, &Bc, &out, &ops_arg};
+    // the prefix stages run pfx_sets frame sets per wave in the same per-set layout
+    const size_t lds = (size_t)((d->lds_bytes - d->lds_tab_bytes) / d->sets * sets + d->lds_tab_bytes);
+    const int rc = timed_launch(d, prefix ? QPD_KC_PFX : QPD_KC_DECODE, st, [&]() -> int {
+        QPD_HIP(hipLaunchKernel(kfn, dim3(fgrid), dim3(64), args, lds, st));
+        QPD_HIP(hipGetLastError());
+        return QPD_OK;
+    });
+    if (!rc) d->task_base += (uint32_t)fgroups;  // takes of this launch (wave_take)
+    return rc;
+}
+
+// FastPlan::pfx_geo of a prefix stage with 2^ps paths per frame: 64 >> ps frames of 2^ps paths per 64 words.
+constexpr int prefix_geo(int ps) { return (6 - ps) | (ps << 8); }
+static_assert(prefix_geo(0) == 6 && prefix_geo(1) == (5 | (1 << 8)) && prefix_geo(2) == (4 | (2 << 8)), "stages 1, 1b, 2");
+
+// The decode of Bc frames from their root pre-pass rows (pre-mode decoders).
+int decode_pre_rows(qpd_decoder *d, const uint32_t *rows, int64_t Bc, uint8_t *out, hipStream_t st) {
+    qpd::FastPlan fp = d->fplan;
+    fp.in_vec = 1;
+    fp.in_shift = fp.n - 2;
+    if (d->pfx[0].nops > 0) {  // the frozen-prefix stages, then the decode
+        int rc = QPD_OK;
+        for (auto &sg : d->pfx)
+            if (!rc && sg.nops > 0) rc = ensure_records(sg.buf, sg.cap, Bc, sg.rec, sg.paths);
+        if (!rc) rc = patch_imports(d, st);
+        if (rc) return rc;
+        qpd::FastPlan pp = fp;
+        const qpd::MOp *ops = (const qpd::MOp *)d->pfx_mops.p;
+        for (const auto &sg : d->pfx) {  // each stage with ops: `paths` lanes and list entries per frame
+            if (sg.nops > 0) {
+                const int ps = __builtin_ctz(sg.paths);
+                pp.ops = ops;
+                pp.nops = sg.nops;
+                pp.gs = pp.L = sg.paths;
+                pp.fpw = 64 >> ps;
+                pp.pfx = (uint32_t *)sg.buf.p;
+                pp.pfx_rec = sg.rec;
+                pp.pfx_geo = prefix_geo(ps);
+                pp.pm_off = sg.pm;
+                if ((rc = fast_launch(d, pp, (const int32_t *)rows, Bc, nullptr, st, true))) return rc;
+            }
+            ops += sg.nops;
+        }
+    }
+    return fast_launch(d, fp, (const int32_t *)rows, Bc, out, st);
+}
+
+// Pre-pass rows (N bytes per frame) for up to d->pre_chunk of B frames: the
+// frames per chunk.
+int64_t reserve_pre_rows(qpd_decoder *d, int64_t B, int *rc) {
+    return d->pre_rows.reserve(std::min<int64_t>(B, d->pre_chunk), (size_t)d->N, "pre-pass rows hipMalloc: ", rc);
+}
+
+// int32 symbols of at most `lim` of B frames, or 1 GB of them (2^18 frames at
+// N = 1024), in a staging buffer: the frames per chunk.
+int64_t reserve_symbols(qpd_decoder *d, DeviceChunk &buf, int64_t B, int64_t lim, const char *what, int *rc) {
+    if (!lim) lim = std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)d->N * 4));
+    return buf.reserve(std::min<int64_t>(B, lim), (size_t)d->N * sizeof(int32_t), what, rc);
+}
+
+// Pre-mode: the root pre-pass on the channel symbols (int32, or uint8 read as
+// they are), then the decode on its rows, chunk by chunk.  fp.in_vec: the
+// symbol rows allow the reader's vector loads (chan_word8).
+template <class In>
+int decode_pre_mode(qpd_decoder *d, qpd::FastPlan fp, const In *d_symbols, int64_t B, uint8_t *d_out, hipStream_t st) {
+    int rc = QPD_OK;
+    const int64_t chunk = reserve_pre_rows(d, B, &rc);
+    if (rc) return rc;
+    uint32_t *pre = (uint32_t *)d->pre_rows.p;
+    for (int64_t f0 = 0; f0 < B; f0 += chunk) {
+        int64_t Bc = std::min<int64_t>(chunk, B - f0);
+        const In *sym = d_symbols + f0 * fp.N;
+        fp.in_shift = fp.n;
+        const int pgrid = (int)std::min<int64_t>(((Bc << (fp.n - 4)) + 255) / 256, 8192);
+        void *pargs[] = {&fp, &sym, &Bc, &pre};
+        rc = timed_launch(d, QPD_KC_PRE, st, [&]() -> int {
+            QPD_HIP(hipLaunchKernel(reinterpret_cast<const void *>(&qpd::root_pre_kernel<In>), dim3(pgrid), dim3(256),
+                                    pargs, 0, st));
+            QPD_HIP(hipGetLastError());
+            return QPD_OK;
+        });
+        if (rc) return rc;
+        rc = decode_pre_rows(d, pre, Bc, d_out + f0 * fp.out_k, st);
+        if (rc) return rc;
+    }
+    return QPD_OK;
+}
+
+int decode_impl(qpd_decoder *d, const int32_t *d_symbols, int64_t B, uint8_t *d_out, hipStream_t st) {
+    d->last_engine = QPD_RAN_GPU;
+    d->u8_staged = 0;
+    if (d->engine != QPD_ENGINE_FAST) {
+        const int64_t groups = (B + d->plan.fpw - 1) / d->plan.fpw;
+        return launch_generic(d, d_symbols, B, d_out, (int)std::min<int64_t>(groups, d->max_waves), st);
+    }
+    qpd::FastPlan fp = d->fplan;
+    fp.in_vec = ((uintptr_t)d_symbols & 15u) == 0 && (fp.N & 3) == 0;
+    if (!d->pre) {
+        fp.in_shift = fp.n;
+        return fast_launch(d, fp, d_symbols, B, d_out, st);
+    }
+    return decode_pre_mode(d, fp, d_symbols, B, d_out, st);
+}
+
+// uint8 channel symbols (caller: lock held, stream ordered).  Pre-mode reads
+// them as they are (root_pre_kernel<uint8_t>); everything else widens a chunk
+// into the int32 staging buffer on the same stream and runs the int32 launch.
+int decode_u8_impl(qpd_decoder *d, const uint8_t *d_symbols, int64_t B, uint8_t *d_out, hipStream_t st) {
+    if (d->engine == QPD_ENGINE_FAST && d->pre) {
+        d->last_engine = QPD_RAN_GPU;
+        d->u8_staged = 0;
+        qpd::FastPlan fp = d->fplan;
+        fp.in_vec = ((uintptr_t)d_symbols & 7u) == 0;  // N >= 16: every row and half keeps the base's alignment
+        return decode_pre_mode(d, fp, d_symbols, B, d_out, st);
+    }
+    int rc = QPD_OK;
+    const int64_t chunk = reserve_symbols(d, d->u8_sym, B, d->u8_chunk, "uint8 staging hipMalloc: ", &rc);
+    if (rc) return rc;
+    int32_t *stage = (int32_t *)d->u8_sym.p;
+    for (int64_t f0 = 0; f0 < B; f0 += chunk) {
+        const int64_t Bc = std::min<int64_t>(chunk, B - f0);
+        const int64_t n = Bc * d->N;
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n / 4 + 255) / 256, 8192));
+        hipLaunchKernelGGL(qpd::widen_u8_kernel, dim3(grid), dim3(256), 0, st, d_symbols + f0 * d->N, n, stage);
+        QPD_HIP(hipGetLastError());
+        if ((rc = decode_impl(d, stage, Bc, d_out + f0 * d->out_bits, st))) return rc;
+    }
+    d->u8_staged = 1;
+    return QPD_OK;
+}
+
+int decode_f64_impl(qpd_decoder *d, const double *d_llr, int64_t B, uint8_t *d_out, hipStream_t st) {
+    d->last_engine = QPD_RAN_GPU;
+    d->u8_staged = 0;
+    const int64_t groups = (B + d->plan.fpw - 1) / d->plan.fpw;
+    const int grid = (int)std::min<int64_t>(groups, d->max_waves);
+    return launch_generic(d, d_llr, B, d_out, grid, st);
+}
+
+// The checks the decode entry points share.  *run = false where there is
+// nothing to decode (a refusal, or an empty batch: QPD_OK).  lut: the entry
+// point takes LUT symbols (qpd_decode, qpd_decode_u8), not LLRs
+// (qpd_decode_f64); suffix: "" or, for the host-buffer entry points, "_host".
+int check_decode_args(const qpd_decoder *d, bool lut, const char *suffix, int64_t B, const void *in, const void *out,
+                      bool *run) {
+    *run = false;
+    if (!d) return fail(QPD_E_INVALID, "null decoder");
+    if (lut != (d->dom == qpd::DOM_LUT))
+        return fail(QPD_E_INVALID, std::string(lut ? "this decoder takes float64 LLRs: use qpd_decode_f64"
+                                                   : "LUT decoders take int32 channel symbols: use qpd_decode") + suffix);
+    if (B < 0) return fail(QPD_E_INVALID, "negative batch");
+    if (B == 0) return QPD_OK;
+    if (!in || !out) return fail(QPD_E_INVALID, "null buffer");
+    *run = true;
+    return QPD_OK;
+}
+
+}  // namespace

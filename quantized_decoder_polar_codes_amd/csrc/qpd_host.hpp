@@ -4,11 +4,11 @@
 // mainFPDecoder.py:113).  A GPU launch costs ~0.1 ms before any decoding
 // (launch, copies, synchronization), ten times the reference's whole SC-LUT
 // call at N = 128 (SCLUTDecoder.cpp:21-124, ~10 us), so the host-buffer entry
-// points send batches this small here (qpd_capi.hip: host_engine_takes).
+// points send batches this small here (qpd_capi_host.hpp: host_engine_takes).
 // Batches go to the GPU kernels; this engine is product code with its own
 // parity tests (tests/test_gpu_host_engine.py), not the test oracle.
 //
-// Same algorithm as the GPU kernels (the static schedule of qpd_capi.hip:
+// Same algorithm as the GPU kernels (the static schedule of qpd_schedule.hpp:
 // visit, pointer memory instead of the reference's per-fork deep copies,
 // the reference's mink / argsort ties through stl_sort.hpp), laid out for one
 // core: per path byte / double arrays per tree depth, an F or G whose inputs

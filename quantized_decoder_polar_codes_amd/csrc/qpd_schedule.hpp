@@ -1,5 +1,5 @@
 // qpd_schedule.hpp -- the static traversal schedule (host code), shared by
-// the C-ABI (qpd_capi.hip: GPU plans) and the host engine (qpd_host.hpp).
+// the C-ABI (qpd_capi_build.hpp: GPU plans) and the host engine (qpd_host.hpp).
 #pragma once
 #include <algorithm>
 #include <cstdint>

@@ -4,7 +4,7 @@ call under the GIL, py_SCLLUTDecoder.cpp:15).
 
 A decoder owns work buffers (global slab, pre-pass rows, task-queue counter,
 error word, host staging), so calls on different streams must not overlap.
-The library orders them itself (qpd_capi.hip: order_on / mark_on, a per-handle
+The library orders them itself (qpd_decoder.hpp: order_on / mark_on, a per-handle
 mutex).  Each test issues work that WOULD overlap without that ordering -- a
 large decode still running on one stream when the next call starts on another
 -- and checks every result against the oracle or a separately decoded copy.
