@@ -270,6 +270,33 @@ int qpd_mc_frames(qpd_decoder *dec, const qpd_mc_channel *ch, uint64_t seed, int
  * in one call. */
 int qpd_mc_decode(qpd_decoder *dec, const qpd_mc_channel *ch, uint64_t seed, int64_t frame0, int64_t B,
                   uint8_t *d_msg, uint8_t *d_out, int64_t *d_counts, void *stream);
+/*
+ * The same frames for the float64-LLR decoders (the drivers mainFPDecoder.py and
+ * mainQuantizedDecoder_ContinuousDomain.py): d_llr, device float64 [B][N], holds
+ * the LLRs 2y/sigma^2 themselves -- the doubles qpd_mc_frames quantizes, so for
+ * one (seed, frame id) a float decoder and a LUT decoder of the same code see the
+ * same message and noise, and quantizing d_llr with the driver's rule gives
+ * qpd_mc_frames' symbols bit for bit.  Any decoder kind (the code is what counts);
+ * d_msg as for qpd_mc_frames.  d_llr needs 8-byte alignment; 16 is faster.
+ * rec == NULL: only ch->sigma is read (edges / lut may be NULL, n_edges 0).
+ * rec != NULL (host [q], finite, q <= 256): the continuous-domain driver's channel
+ * quantizer -- d_llr holds rec[s], s the symbol qpd_mc_frames writes for that LLR
+ * (saturations included; a uniform and a Lloyd design are both edges plus
+ * reconstruction values).
+ * A CRC-aided decoder whose K - A exceeds crc_n (QPD_CASCL_FLOAT with
+ * A + crc_n < K) has no CRC bits to fill its message with: QPD_E_UNSUPPORTED.
+ */
+int qpd_mc_llr(qpd_decoder *dec, const qpd_mc_channel *ch, const double *rec, uint64_t seed, int64_t frame0, int64_t B,
+               uint8_t *d_msg, double *d_llr, void *stream);
+/* qpd_mc_llr's frames, decoded: d_out = what qpd_decode_f64 returns for them
+ * (float64-LLR kinds only: QPD_SC_FLOAT, 7..14; QPD_E_INVALID otherwise); d_msg,
+ * d_counts, stream ordering and qpd_info.last_engine as for qpd_mc_decode.  The
+ * LLRs pass through a buffer of the decoder's own, chunk by chunk:
+ *     frames per chunk = max(1, 2^28 / (8 N))      (at most 256 MB of LLRs;
+ * halved while the allocation fails, like the other chunk buffers), each chunk
+ * generated, then decoded, then the counters over the whole range. */
+int qpd_mc_decode_f64(qpd_decoder *dec, const qpd_mc_channel *ch, const double *rec, uint64_t seed, int64_t frame0,
+                      int64_t B, uint8_t *d_msg, uint8_t *d_out, int64_t *d_counts, void *stream);
 
 /*
  * Offline table design (host code, no device needed) -- the reference's
@@ -334,7 +361,8 @@ typedef struct qpd_info {
                                  0: int32 and float64 calls, host-engine runs, uint8 read directly */
 } qpd_info;
 /* qpd_info.last_engine: no decode yet, the GPU kernels (qpd_decode*, the GPU
- * branch of the host-buffer calls, qpd_mc_decode), or the host engine. */
+ * branch of the host-buffer calls, qpd_mc_decode, qpd_mc_decode_f64), or the
+ * host engine. */
 enum qpd_ran { QPD_RAN_NONE = 0, QPD_RAN_GPU = 1, QPD_RAN_HOST = 2 };
 int qpd_get_info(const qpd_decoder *dec, qpd_info *info);
 
@@ -348,7 +376,7 @@ int qpd_get_info(const qpd_decoder *dec, qpd_info *info);
 enum qpd_kernel_class {
     QPD_KC_PRE = 0,    /* root_pre_kernel (fast engine, root pre-pass)              */
     QPD_KC_DECODE = 1, /* lut_fast_kernel / generic_decode_kernel                   */
-    QPD_KC_MC = 2,     /* mc_frames_kernel (qpd_mc_frames)                          */
+    QPD_KC_MC = 2,     /* mc_frames_kernel (qpd_mc_frames, qpd_mc_llr, both fused calls) */
     QPD_KC_PFX = 3,    /* lut_prefix_kernel (fast engine, frozen prefix of list kinds) */
     QPD_KC_COUNT = 4
 };

@@ -38,6 +38,8 @@ EXPORTED = (
     "qpd_get_info",
     "qpd_mc_frames",
     "qpd_mc_decode",
+    "qpd_mc_llr",
+    "qpd_mc_decode_f64",
     "qpd_optls_quantizer",
     "qpd_lutgen_mindistortion",
     "qpd_profile",
@@ -182,6 +184,10 @@ def load():
     L.qpd_mc_frames.restype = ctypes.c_int
     L.qpd_mc_decode.argtypes = [_P, ctypes.POINTER(QpdMcChannel), ctypes.c_uint64, _i64, _i64, _P, _P, _P, _P]
     L.qpd_mc_decode.restype = ctypes.c_int
+    L.qpd_mc_llr.argtypes = [_P, ctypes.POINTER(QpdMcChannel), _P, ctypes.c_uint64, _i64, _i64, _P, _P, _P]
+    L.qpd_mc_llr.restype = ctypes.c_int
+    L.qpd_mc_decode_f64.argtypes = [_P, ctypes.POINTER(QpdMcChannel), _P, ctypes.c_uint64, _i64, _i64, _P, _P, _P, _P]
+    L.qpd_mc_decode_f64.restype = ctypes.c_int
     L.qpd_optls_quantizer.argtypes = [_P, _P, _i32, _i32, _i32, _P, _P, _P, _P]
     L.qpd_optls_quantizer.restype = ctypes.c_int
     L.qpd_lutgen_mindistortion.argtypes = [_i32, _i32, _P, _P, _i32, _i32, _P, _P, _P, _P]

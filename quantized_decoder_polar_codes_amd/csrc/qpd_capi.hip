@@ -164,7 +164,7 @@ int qpd_mc_frames(qpd_decoder *d, const qpd_mc_channel *ch, uint64_t seed, int64
     const int rc = check_mc_args(d, ch, false, frame0, B, d_msg, d_symbols, &run);
     if (!run) return rc;
     hipStream_t st = (hipStream_t)stream;
-    return ordered(d, st, [&]() { return mc_launch(d, ch, seed, frame0, B, d_msg, d_symbols, false, st); });
+    return ordered(d, st, [&]() { return mc_launch(d, ch, seed, frame0, B, d_msg, d_symbols, qpd::MC_SYM, st); });
 }
 
 int qpd_mc_decode(qpd_decoder *d, const qpd_mc_channel *ch, uint64_t seed, int64_t frame0, int64_t B, uint8_t *d_msg,
@@ -174,6 +174,26 @@ int qpd_mc_decode(qpd_decoder *d, const qpd_mc_channel *ch, uint64_t seed, int64
     if (!run) return rc;
     hipStream_t st = (hipStream_t)stream;
     return ordered(d, st, [&]() { return mc_decode(d, ch, seed, frame0, B, d_msg, d_out, d_counts, st); });
+}
+
+int qpd_mc_llr(qpd_decoder *d, const qpd_mc_channel *ch, const double *rec, uint64_t seed, int64_t frame0, int64_t B,
+               uint8_t *d_msg, double *d_llr, void *stream) {
+    bool run;
+    const int rc = check_mc_llr_args(d, ch, rec, false, frame0, B, d_msg, d_llr, &run);
+    if (!run) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return ordered(d, st, [&]() {
+        return mc_launch(d, ch, seed, frame0, B, d_msg, d_llr, rec ? qpd::MC_LLR_REC : qpd::MC_LLR, st, rec);
+    });
+}
+
+int qpd_mc_decode_f64(qpd_decoder *d, const qpd_mc_channel *ch, const double *rec, uint64_t seed, int64_t frame0,
+                      int64_t B, uint8_t *d_msg, uint8_t *d_out, int64_t *d_counts, void *stream) {
+    bool run;
+    const int rc = check_mc_llr_args(d, ch, rec, true, frame0, B, d_msg, d_out, &run);
+    if (!run) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return ordered(d, st, [&]() { return mc_decode_f64(d, ch, rec, seed, frame0, B, d_msg, d_out, d_counts, st); });
 }
 
 int qpd_probe_lds(int32_t device, int32_t op, double *gbps) {

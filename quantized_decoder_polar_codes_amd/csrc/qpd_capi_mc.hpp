@@ -2,6 +2,7 @@
 // check, the frame generator's launch (qpd_mc.hip), and generate + decode +
 // count chunk by chunk.  Host code.
 #pragma once
+#include <cmath>
 #include <cstring>
 
 #include "qpd_capi_decode.hpp"
@@ -19,6 +20,40 @@ int check_channel(const qpd_mc_channel *ch) {
         if (ch->lut[i] < 0 || ch->lut[i] >= ch->q) return fail(QPD_E_INVALID, "lut entry outside [0, q)");
     }
     return QPD_OK;
+}
+
+// The LLR entry points' channel.  Without rec the quantizer is unused (edges /
+// lut may be null, n_edges 0): only sigma counts.  With rec: a whole channel
+// quantizer, and one finite reconstruction value per symbol (the generator
+// stages up to 256 of them).
+int check_llr_channel(const qpd_mc_channel *ch, const double *rec) {
+    if (!rec) return ch->sigma > 0 ? QPD_OK : fail(QPD_E_INVALID, "sigma must be > 0");
+    const int rc = check_channel(ch);
+    if (rc) return rc;
+    if (ch->q > qpd::kMcMaxEdges - 1) return fail(QPD_E_INVALID, "rec: q must be at most 256");
+    for (int i = 0; i < ch->q; ++i)
+        if (!std::isfinite(rec[i])) return fail(QPD_E_INVALID, "rec entries must be finite");
+    return QPD_OK;
+}
+
+// The checks the two LLR entry points share (as check_mc_args).  f64_only: the
+// entry point decodes too (qpd_mc_decode_f64), so it needs a float64-LLR decoder.
+int check_mc_llr_args(const qpd_decoder *d, const qpd_mc_channel *ch, const double *rec, bool f64_only, int64_t frame0,
+                      int64_t B, const void *d_msg, const void *d_buf, bool *run) {
+    *run = false;
+    if (!d || !ch) return fail(QPD_E_INVALID, "null argument");
+    if (f64_only && d->dom == qpd::DOM_LUT)
+        return fail(QPD_E_INVALID, "qpd_mc_decode_f64 needs a float64-LLR decoder: use qpd_mc_decode");
+    // the generator appends K - A bits of the crc_n-bit CRC; QPD_CASCL_FLOAT compares
+    // exactly crc_n, so it is served where A + crc_n == K (the driver's own case)
+    if (d->crc_n > 0 && d->K - d->ca_A > d->crc_n)
+        return fail(QPD_E_UNSUPPORTED, "Monte-Carlo frames of a CRC-aided decoder need K - A <= crc_n (CASCLDecoder: A + crc_n == K)");
+    if (B < 0 || frame0 < 0) return fail(QPD_E_INVALID, "negative frame range");
+    if (B == 0) return QPD_OK;
+    if (!d_msg || !d_buf) return fail(QPD_E_INVALID, "null buffer");
+    const int rc = check_llr_channel(ch, rec);
+    *run = !rc;
+    return rc;
 }
 
 // The checks the two Monte-Carlo entry points share.  *run = false where there
@@ -64,12 +99,43 @@ int mc_constants(qpd_decoder *d) {
     return rc ? rc : upload(d->mc_crc, tab.data(), tab.size(), d->hs);
 }
 
-// The Monte-Carlo generator on stream st: int32 symbols to `rows`, or (pre)
-// the decoder's root pre-pass rows.  Caller: lock held, stream ordered.
+// The device copy of the reconstruction table (MC_LLR_REC), uploaded on stream
+// st when it differs from the last call's, complete on return: the caller's
+// array is not read after the call, and launches queued earlier (st is ordered
+// after them) have read the previous table.
+int mc_rec_table(qpd_decoder *d, const double *rec, int q, hipStream_t st) {
+    if (!d->mc_rec.p) QPD_HIP(hipMalloc(&d->mc_rec.p, (qpd::kMcMaxEdges - 1) * sizeof(double)));
+    if ((int)d->mc_rec_host.size() == q && std::equal(rec, rec + q, d->mc_rec_host.begin(), [](double a, double b) {
+            return std::memcmp(&a, &b, sizeof a) == 0;
+        }))
+        return QPD_OK;
+    d->mc_rec_host.clear();  // no table on the device until the copy below is complete
+    QPD_HIP(hipMemcpyAsync(d->mc_rec.p, rec, q * sizeof(double), hipMemcpyHostToDevice, st));
+    QPD_HIP(hipStreamSynchronize(st));
+    d->mc_rec_host.assign(rec, rec + q);
+    return QPD_OK;
+}
+
+const void *mc_kernel(int mode) {
+    switch (mode) {
+        case qpd::MC_SYM: return reinterpret_cast<const void *>(&qpd::mc_frames_kernel<qpd::MC_SYM>);
+        case qpd::MC_PRE: return reinterpret_cast<const void *>(&qpd::mc_frames_kernel<qpd::MC_PRE>);
+        case qpd::MC_LLR: return reinterpret_cast<const void *>(&qpd::mc_frames_kernel<qpd::MC_LLR>);
+        default: return reinterpret_cast<const void *>(&qpd::mc_frames_kernel<qpd::MC_LLR_REC>);
+    }
+}
+
+// The Monte-Carlo generator on stream st, `rows` by mode (qpd::McMode): int32
+// symbols, the decoder's root pre-pass rows, or float64 LLRs (rec: null, or the
+// host table of MC_LLR_REC).  Caller: lock held, stream ordered.
 int mc_launch(qpd_decoder *d, const qpd_mc_channel *ch, uint64_t seed, int64_t frame0, int64_t B, uint8_t *d_msg,
-              int32_t *rows, bool pre, hipStream_t st) {
+              void *rows, int mode, hipStream_t st, const double *rec = nullptr) {
     if (!d->mc_pref.p) {
         const int rc = mc_constants(d);
+        if (rc) return rc;
+    }
+    if (mode == qpd::MC_LLR_REC) {
+        const int rc = mc_rec_table(d, rec, ch->q, st);
         if (rc) return rc;
     }
     qpd::McChannel C;
@@ -89,25 +155,36 @@ int mc_launch(qpd_decoder *d, const qpd_mc_channel *ch, uint64_t seed, int64_t f
     C.crc_tab = (const uint32_t *)d->mc_crc.p;
     C.f_tab = d->fplan.f_tab;
     C.g_tab = d->fplan.g_tab;
-    for (int i = 0; i < ch->n_edges; ++i) C.edges[i] = ch->edges[i];
-    for (int i = 0; i + 1 < ch->n_edges; ++i) C.lut[i] = ch->lut[i];
+    if (mode == qpd::MC_LLR_REC) C.rec = (const double *)d->mc_rec.p;  // in f_tab's place (McChannel)
+    if (mode != qpd::MC_LLR) {  // MC_LLR: no quantizer (the channel's may be absent)
+        for (int i = 0; i < ch->n_edges; ++i) C.edges[i] = ch->edges[i];
+        for (int i = 0; i + 1 < ch->n_edges; ++i) C.lut[i] = ch->lut[i];
+    } else {
+        C.n_edges = 0;
+    }
     int per_cu = 0;
     const int ncu = device_cus();
-    const size_t lds = qpd::mc_lds_bytes(d->N, d->K, pre);
+    const size_t lds = qpd::mc_lds_bytes(d->N, d->K, mode);
     // one resident round of workgroups (grid-stride over frames): a grid
     // larger than what fits at once runs its last workgroups as a tail
-    const void *kfn = pre ? reinterpret_cast<const void *>(&qpd::mc_frames_kernel<true>)
-                          : reinterpret_cast<const void *>(&qpd::mc_frames_kernel<false>);
+    const void *kfn = mc_kernel(mode);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 64, lds) != hipSuccess || per_cu <= 0) per_cu = 8;
     const int grid = (int)std::min<int64_t>(B, (int64_t)ncu * per_cu);
+    void *args[] = {&C, &frame0, &B, &d_msg, &rows};
     return timed_launch(d, QPD_KC_MC, st, [&]() -> int {
-        if (pre)
-            hipLaunchKernelGGL(qpd::mc_frames_kernel<true>, dim3(grid), dim3(64), lds, st, C, frame0, B, d_msg, rows);
-        else
-            hipLaunchKernelGGL(qpd::mc_frames_kernel<false>, dim3(grid), dim3(64), lds, st, C, frame0, B, d_msg, rows);
+        QPD_HIP(hipLaunchKernel(kfn, dim3(grid), dim3(64), args, lds, st));
         QPD_HIP(hipGetLastError());
         return QPD_OK;
     });
+}
+
+// Bit and block errors of B decoded frames against their messages, added to d_counts.
+int mc_count(qpd_decoder *d, const uint8_t *d_out, const uint8_t *d_msg, int64_t B, int64_t *d_counts, hipStream_t st) {
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((B + 3) / 4, (int64_t)device_cus() * 8));
+    hipLaunchKernelGGL(qpd::mc_count_kernel, dim3(grid), dim3(256), 0, st, d_out, d_msg, B, d->out_bits,
+                       (unsigned long long *)d_counts);
+    QPD_HIP(hipGetLastError());
+    return QPD_OK;
 }
 
 // qpd_mc_decode's work on stream st (caller: lock held, stream ordered):
@@ -127,20 +204,36 @@ int mc_decode(qpd_decoder *d, const qpd_mc_channel *ch, uint64_t seed, int64_t f
     void *buf = fused ? d->pre_rows.p : d->mc_sym.p;
     for (int64_t f0 = 0; f0 < B; f0 += chunk) {
         const int64_t Bc = std::min<int64_t>(chunk, B - f0);
-        int r = mc_launch(d, ch, seed, frame0 + f0, Bc, d_msg + f0 * d->out_bits, (int32_t *)buf, fused, st);
+        int r = mc_launch(d, ch, seed, frame0 + f0, Bc, d_msg + f0 * d->out_bits, buf, fused ? qpd::MC_PRE : qpd::MC_SYM, st);
         if (r) return r;
         uint8_t *out = d_out + f0 * d->out_bits;
         r = fused ? decode_pre_rows(d, (const uint32_t *)buf, Bc, out, st)
                   : decode_impl(d, (const int32_t *)buf, Bc, out, st);
         if (r) return r;
     }
-    if (d_counts) {  // the driver's error counters over the whole range
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((B + 3) / 4, (int64_t)device_cus() * 8));
-        hipLaunchKernelGGL(qpd::mc_count_kernel, dim3(grid), dim3(256), 0, st, d_out, d_msg, B, d->out_bits,
-                           (unsigned long long *)d_counts);
-        QPD_HIP(hipGetLastError());
+    // the driver's error counters over the whole range
+    return d_counts ? mc_count(d, d_out, d_msg, B, d_counts, st) : QPD_OK;
+}
+
+// qpd_mc_decode_f64's work on stream st (caller: lock held, stream ordered):
+// a chunk of LLRs generated into the decoder's own buffer (mc_llr_chunk_frames,
+// qpd_chunk.hpp; fewer after an allocation failure), decoded, and so on; then
+// the counters over the whole range.
+int mc_decode_f64(qpd_decoder *d, const qpd_mc_channel *ch, const double *rec, uint64_t seed, int64_t frame0, int64_t B,
+                  uint8_t *d_msg, uint8_t *d_out, int64_t *d_counts, hipStream_t st) {
+    int rc = QPD_OK;
+    const int64_t chunk = d->mc_llr.reserve(std::min<int64_t>(B, qpd::mc_llr_chunk_frames(d->N)), (size_t)d->N * sizeof(double),
+                                            "Monte-Carlo LLRs hipMalloc: ", &rc);
+    if (rc) return rc;
+    double *buf = (double *)d->mc_llr.p;
+    for (int64_t f0 = 0; f0 < B; f0 += chunk) {
+        const int64_t Bc = std::min<int64_t>(chunk, B - f0);
+        if ((rc = mc_launch(d, ch, seed, frame0 + f0, Bc, d_msg + f0 * d->out_bits, buf, rec ? qpd::MC_LLR_REC : qpd::MC_LLR,
+                            st, rec)))
+            return rc;
+        if ((rc = decode_f64_impl(d, buf, Bc, d_out + f0 * d->out_bits, st))) return rc;
     }
-    return QPD_OK;
+    return d_counts ? mc_count(d, d_out, d_msg, B, d_counts, st) : QPD_OK;
 }
 
 }  // namespace

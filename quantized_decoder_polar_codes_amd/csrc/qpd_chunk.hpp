@@ -39,4 +39,8 @@ struct ChunkBuf {
     }
 };
 
+// qpd_mc_decode_f64's frames per chunk (qpd.h): 2^28 bytes (256 MB) of float64
+// LLRs, at least one frame.
+inline int64_t mc_llr_chunk_frames(int N) { return std::max<int64_t>(1, ((int64_t)1 << 28) / (8 * (int64_t)N)); }
+
 }  // namespace qpd

@@ -100,6 +100,9 @@ struct qpd_decoder {
     int64_t pre_chunk = 0;    // frames per pre-pass chunk
     DeviceChunk pre_rows;     // pre-pass rows of one chunk (N bytes per frame)
     DeviceChunk mc_sym;       // qpd_mc_decode without a fused pre-pass: int32 symbols of one chunk
+    DeviceChunk mc_llr;       // qpd_mc_decode_f64: float64 LLRs of one chunk (qpd_chunk.hpp: mc_llr_chunk_frames)
+    DeviceBuf mc_rec;         // qpd_mc_llr / qpd_mc_decode_f64 with rec: the reconstruction table's device copy
+    std::vector<double> mc_rec_host;  // what mc_rec holds (empty: nothing)
     DeviceChunk u8_sym;       // qpd_decode_u8 outside pre-mode: int32 symbols of one chunk (widen_u8_kernel)
     int64_t u8_chunk = 0;    // QPD_U8_CHUNK (tests): frames per staging chunk (0: 1 GB of int32 symbols)
     int u8_staged = 0;       // qpd_info.u8_staged: the last decode call widened its input into u8_sym

@@ -34,6 +34,16 @@
 // encoder runs 5 in-word butterfly stages as shift/mask XORs plus log2(N/32)
 // word stages in LDS.  Noise, LLR and quantizer: one position pair per lane
 // and round, stored as int2 (512 B per wave-instruction, coalesced).
+//
+// LLR modes (qpd_mc_llr, qpd_mc_decode_f64): the frame's N float64 LLRs instead
+// of symbols, row-major [B][N] -- the very doubles the symbol mode bisects, so
+// quantizing them on the host gives its symbols bit for bit.  One 16-byte store
+// per lane (1 KB of consecutive bytes per wave-instruction); two 8-byte stores
+// from a base that is only 8-byte aligned (N is even: every row keeps the
+// base's alignment).  MC_LLR compiles the quantizer and its LDS tables out;
+// MC_LLR_REC runs it and stores rec[symbol], the continuous-domain driver's
+// channel quantizer (mainQuantizedDecoder_ContinuousDomain.py) in this
+// library's edge convention, saturations included.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -87,7 +97,14 @@ struct McChannel {
     // of int32 symbols, each frame's root pre-pass row (root_pre_kernel's
     // layout: f(y), g(y, 0), g(y, 1) as nibble words, N/4 dwords per frame),
     // computed from the frame's symbols staged in LDS with the root's tables.
-    const uint32_t *f_tab, *g_tab;  // node 0's nibble tables (FastPlan f_tab / g_tab)
+    // MC_LLR_REC: reconstruction value per symbol, [q] with q <= 256 (device;
+    // staged in LDS).  In f_tab's place, which only PRE mode reads: the struct
+    // keeps its size, and the other modes' kernel arguments their offsets.
+    union {
+        const uint32_t *f_tab;  // node 0's nibble tables (FastPlan f_tab / g_tab)
+        const double *rec;
+    };
+    const uint32_t *g_tab;
 };
 
 // The double 1.m in [1, 2) whose 52 mantissa bits are (a >> 12) : b -- two
@@ -166,11 +183,17 @@ __device__ inline double mc_log(double u) {
 #ifndef QPD_MC_WPE
 #define QPD_MC_WPE 6  // 6 waves per SIMD: -2.5 % generator time vs 5 (profiles/r03j_ab_generator.txt)
 #endif
-template <bool PRE>
+// What the generator writes per frame: int32 symbols, the root pre-pass row,
+// the float64 LLRs, or the reconstruction values of the LLRs' symbols.
+enum McMode { MC_SYM = 0, MC_PRE = 1, MC_LLR = 2, MC_LLR_REC = 3 };
+template <int MODE>
 __global__ __launch_bounds__(64, QPD_MC_WPE) void mc_frames_kernel(McChannel C, int64_t frame0, int64_t B,
                                                        uint8_t *__restrict__ msg_out, int32_t *__restrict__ sym_out) {
 #pragma clang fp contract(off)
     extern __shared__ uint32_t lds_mc[];
+    constexpr bool PRE = MODE == MC_PRE;
+    constexpr bool LLR = MODE == MC_LLR || MODE == MC_LLR_REC;  // sym_out holds doubles, N per frame
+    constexpr bool QUANT = MODE != MC_LLR;                      // the channel quantizer runs
     // PRE: sym_out holds pre-pass rows (N/4 dwords per frame), see McChannel
     uint32_t Tf = 0, Tg = 0;
     if (PRE) {
@@ -183,14 +206,20 @@ __global__ __launch_bounds__(64, QPD_MC_WPE) void mc_frames_kernel(McChannel C, 
     const int kw = (K + 31) >> 5;        // information-bit words (message + CRC)
     // E[0] = -inf, E[1 + i] = edges[i]: E[lo] = edges[lo - 1] and E[lo + 1] = edges[lo] need no guards
     double *E = reinterpret_cast<double *>(lds_mc);
-    int32_t *lut = reinterpret_cast<int32_t *>(E + kMcMaxEdges + 1);
-    uint32_t *xw = reinterpret_cast<uint32_t *>(lut + kMcMaxEdges);
+    double *rec = E + kMcMaxEdges + 1;  // MC_LLR_REC: [kMcMaxEdges - 1]
+    int32_t *lut = reinterpret_cast<int32_t *>(rec + (MODE == MC_LLR_REC ? kMcMaxEdges - 1 : 0));
+    uint32_t *xw = QUANT ? reinterpret_cast<uint32_t *>(lut + kMcMaxEdges) : lds_mc;  // MC_LLR: no tables
     uint32_t *bw = xw + nw;               // message + CRC bits (kw + 2 words)
     uint8_t *sy = reinterpret_cast<uint8_t *>(bw + kw + 2);  // PRE: the frame's N channel symbols
-    for (int i = t; i < C.n_edges; i += 64) E[1 + i] = C.edges[i];
-    if (t == 0) E[0] = -__builtin_inf();
-    for (int i = t; i < M; i += 64) lut[i] = C.lut[i];
-    const double lo_edge = C.edges[0], hi_edge = C.edges[M];
+    if constexpr (QUANT) {
+        for (int i = t; i < C.n_edges; i += 64) E[1 + i] = C.edges[i];
+        if (t == 0) E[0] = -__builtin_inf();
+        for (int i = t; i < M; i += 64) lut[i] = C.lut[i];
+    }
+    if constexpr (MODE == MC_LLR_REC)
+        for (int i = t; i < C.q; i += 64) rec[i] = C.rec[i];
+    const double lo_edge = QUANT ? C.edges[0] : 0.0, hi_edge = QUANT ? C.edges[M] : 0.0;
+    const bool al16 = ((uintptr_t)sym_out & 15u) == 0;  // LLR: one 16-byte store per lane
     const double inv_w = hi_edge > lo_edge ? M / (hi_edge - lo_edge) : 0.0;
     for (int64_t f = blockIdx.x; f < B; f += gridDim.x) {
         const uint64_t gid = (uint64_t)(frame0 + f);
@@ -285,24 +314,39 @@ __global__ __launch_bounds__(64, QPD_MC_WPE) void mc_frames_kernel(McChannel C, 
         auto quantize = [&](int p, const double (&nz)[2]) {
             const uint32_t xbits = xw[(2 * p) >> 5] >> ((2 * p) & 31);
             int s_out[2];
+            double l_out[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const double bpsk = (xbits >> h) & 1u ? -1.0 : 1.0;
                 const double y = bpsk + C.sigma * nz[h];
                 const double llr = y * 2.0 * C.inv_s2;
-                // bisect_left over edges[0..M-1] for lo_edge < llr < hi_edge: lo in [1, M]
-                // with edges[lo - 1] < llr <= edges[lo]; guessed, checked, walked if wrong
-                const bool inner = llr > lo_edge && llr < hi_edge;
-                const double gi = fmin(fmax((llr - lo_edge) * inv_w + 1.0, 1.0), (double)M);
-                int lo = (int)gi;
-                if (inner && !(E[lo] < llr && llr <= E[lo + 1])) {
-                    while (E[lo] >= llr) --lo;     // stops at lo >= 1: E[1] = lo_edge < llr
-                    while (E[lo + 1] < llr) ++lo;  // stops at lo <= M: E[M + 1] = hi_edge > llr
+                if constexpr (QUANT) {
+                    // bisect_left over edges[0..M-1] for lo_edge < llr < hi_edge: lo in [1, M]
+                    // with edges[lo - 1] < llr <= edges[lo]; guessed, checked, walked if wrong
+                    const bool inner = llr > lo_edge && llr < hi_edge;
+                    const double gi = fmin(fmax((llr - lo_edge) * inv_w + 1.0, 1.0), (double)M);
+                    int lo = (int)gi;
+                    if (inner && !(E[lo] < llr && llr <= E[lo + 1])) {
+                        while (E[lo] >= llr) --lo;     // stops at lo >= 1: E[1] = lo_edge < llr
+                        while (E[lo + 1] < llr) ++lo;  // stops at lo <= M: E[M + 1] = hi_edge > llr
+                    }
+                    const int sl = lut[lo - 1];
+                    s_out[h] = inner ? sl : (llr <= lo_edge ? 0 : C.q - 1);
                 }
-                const int sl = lut[lo - 1];
-                s_out[h] = inner ? sl : (llr <= lo_edge ? 0 : C.q - 1);
+                if constexpr (MODE == MC_LLR) l_out[h] = llr;
+                if constexpr (MODE == MC_LLR_REC) l_out[h] = rec[s_out[h]];
             }
-            if (PRE)
+            if constexpr (LLR) {
+                double *o = reinterpret_cast<double *>(sym_out) + f * N + 2 * p;
+                if (al16) {
+                    // a native vector, stored whole (a double2 struct's store is split into its fields)
+                    typedef double f64x2 __attribute__((ext_vector_type(2)));
+                    *reinterpret_cast<f64x2 *>(o) = f64x2{l_out[0], l_out[1]};
+                } else {
+                    o[0] = l_out[0];
+                    o[1] = l_out[1];
+                }
+            } else if (PRE)
                 *reinterpret_cast<uint16_t *>(sy + 2 * p) = (uint16_t)(s_out[0] | (s_out[1] << 8));
             else
                 *reinterpret_cast<int2 *>(sym_out + f * N + 2 * p) = make_int2(s_out[0], s_out[1]);
@@ -397,10 +441,14 @@ __global__ __launch_bounds__(256) void mc_count_kernel(const uint8_t *__restrict
     }
 }
 
-// Dynamic LDS of mc_frames_kernel.
-inline size_t mc_lds_bytes(int N, int K, bool pre) {
-    return (kMcMaxEdges + 1) * sizeof(double) + kMcMaxEdges * sizeof(int32_t) + 4 * (((N + 31) >> 5) + ((K + 31) >> 5) + 2) +
-           (pre ? (size_t)N : 0);
+// Dynamic LDS of mc_frames_kernel<mode>: the quantizer's tables (none in
+// MC_LLR; the reconstruction values too in MC_LLR_REC), the frame's bit words,
+// the staged symbols (MC_PRE).
+inline size_t mc_lds_bytes(int N, int K, int mode) {
+    const size_t tables = mode == MC_LLR ? 0
+                                         : (kMcMaxEdges + 1) * sizeof(double) + kMcMaxEdges * sizeof(int32_t) +
+                                               (mode == MC_LLR_REC ? (kMcMaxEdges - 1) * sizeof(double) : 0);
+    return tables + 4 * (((N + 31) >> 5) + ((K + 31) >> 5) + 2) + (mode == MC_PRE ? (size_t)N : 0);
 }
 
 }  // namespace qpd

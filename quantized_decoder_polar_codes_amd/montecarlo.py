@@ -100,6 +100,75 @@ class GpuFrames:
         return msg, sym
 
 
+def llr_chunk_frames(N: int) -> int:
+    """Frames per chunk of qpd_mc_decode_f64's LLR buffer (include/qpd.h; csrc/qpd_chunk.hpp
+    mc_llr_chunk_frames): 2^28 bytes of float64 LLRs, at least one frame."""
+    return max(1, 2 ** 28 // (8 * int(N)))
+
+
+class GpuLlrFrames:
+    """Frame source of the float64-LLR decoders, backed by qpd_mc_llr / qpd_mc_decode_f64
+    (device tensors): GpuFrames' messages and noise for the same (seed, frame id), as
+    LLRs.  Without ``rec`` the channel quantizer is unused and may be left out; with
+    ``rec`` (one reconstruction value per symbol) the LLRs are re-quantised to
+    ``rec[symbol]`` (the continuous-domain driver's channel quantizer)."""
+
+    def __init__(self, decoder, sigma: float, seed: int, edges=None, lut=None, q: int | None = None, rec=None):
+        import torch
+
+        self.torch = torch
+        self.dec = decoder
+        self.ch = _lib.QpdMcChannel()
+        self.ch.sigma = float(sigma)
+        self.edges = self.lut = self.rec = None
+        if edges is not None:
+            self.edges = np.ascontiguousarray(edges, dtype=np.float64)
+            self.lut = np.ascontiguousarray(lut, dtype=np.int32)
+            self.ch.q = int(q if q is not None else (len(rec) if rec is not None else self.lut.max() + 1))
+            self.ch.n_edges = len(self.edges)
+            self.ch.edges = self.edges.ctypes.data
+            self.ch.lut = self.lut.ctypes.data
+        if rec is not None:
+            if edges is None:
+                raise ValueError("rec needs the channel quantizer it reconstructs (edges, lut)")
+            self.rec = np.ascontiguousarray(rec, dtype=np.float64)
+            if self.rec.size < self.ch.q:
+                raise ValueError(f"rec must have q={self.ch.q} entries, got {self.rec.size}")
+        self.seed = int(seed)
+        self.device = torch.device("cuda", decoder.device if decoder.device >= 0 else torch.cuda.current_device())
+
+    def _rec(self):
+        return ctypes.c_void_p(self.rec.ctypes.data) if self.rec is not None else None
+
+    def decode_frames(self, frame0: int, B: int, counts=None):
+        """(msg, decoded bits) of frames [frame0, frame0+B): the same bits as
+        decode_batch(self(frame0, B)[1]), by qpd_mc_decode_f64 (the LLRs pass through a
+        chunk buffer of the decoder's).  ``counts``: as GpuFrames.decode_frames."""
+        torch = self.torch
+        msg = torch.empty((B, self.dec.out_bits), dtype=torch.uint8, device=self.device)
+        bits = torch.empty((B, self.dec.out_bits), dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        cp = ctypes.c_void_p(counts.data_ptr()) if counts is not None else None
+        _lib.check(_lib.load().qpd_mc_decode_f64(self.dec._h, ctypes.byref(self.ch), self._rec(),
+                                                 ctypes.c_uint64(self.seed), frame0, B, ctypes.c_void_p(msg.data_ptr()),
+                                                 ctypes.c_void_p(bits.data_ptr()), cp, ctypes.c_void_p(stream)))
+        return msg, bits
+
+    def __call__(self, frame0: int, B: int, out=None):
+        """(msg, llr); ``out``: a contiguous float64 CUDA tensor of B*N elements to write
+        the LLRs into (8-byte aligned is enough) instead of a new one."""
+        torch = self.torch
+        msg = torch.empty((B, self.dec.out_bits), dtype=torch.uint8, device=self.device)
+        llr = torch.empty((B, self.dec.N), dtype=torch.float64, device=self.device) if out is None else out
+        if llr.dtype != torch.float64 or not llr.is_contiguous() or llr.numel() != B * self.dec.N:
+            raise ValueError("out must be a contiguous float64 tensor of B*N elements")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(_lib.load().qpd_mc_llr(self.dec._h, ctypes.byref(self.ch), self._rec(), ctypes.c_uint64(self.seed),
+                                          frame0, B, ctypes.c_void_p(msg.data_ptr()), ctypes.c_void_p(llr.data_ptr()),
+                                          ctypes.c_void_p(stream)))
+        return msg, llr.view(B, self.dec.N)
+
+
 def _frame_errors(bits, msg):
     """Per-frame bit-error counts as a 1-D int64 tensor/array."""
     try:
@@ -252,17 +321,27 @@ def run_point(generate, decode, K: int, ebn0_db: float, batch: int, max_blocks: 
 
 def simulate(decoder, msgbits_count: int, ebn0_list, *, seed: int = 2024, batch: int = 1 << 16,
              max_blocks: int = 10 ** 5, stop_blkerrs: int = 1000, edges=None, lut=None, q: int = 16,
-             group=None) -> list:
+             group=None, rec=None) -> list:
     """BER/BLER sweep on the GPU with the decoder's own code (GPU frames,
-    GPU decode, counters all-reduced over ``group`` with RCCL)."""
+    GPU decode, counters all-reduced over ``group`` with RCCL).  A float64-LLR
+    decoder gets the LLRs of the frames a LUT decoder of the same code gets as
+    symbols (GpuLlrFrames; ``rec`` with ``edges`` / ``lut`` re-quantises them, the
+    continuous-domain driver's channel quantizer)."""
     import torch
 
-    if edges is None:
+    float_in = decoder._float_input
+    if rec is not None and not float_in:
+        raise ValueError("rec is for the float64-LLR decoders")
+    if edges is None and (rec is not None or not float_in):
         edges, lut = uniform_channel_quantizer(q)
     rate = msgbits_count / decoder.N
     out = []
     for eb in ebn0_list:
-        src = GpuFrames(decoder, edges, lut, q, sigma_for(eb, rate), point_seed(seed, eb))
+        if float_in:
+            src = GpuLlrFrames(decoder, sigma_for(eb, rate), point_seed(seed, eb),
+                               *((edges, lut, q) if rec is not None else ()), rec=rec)
+        else:
+            src = GpuFrames(decoder, edges, lut, q, sigma_for(eb, rate), point_seed(seed, eb))
         # CRC-aided decoders output A bits: errors are counted over A, and the
         # driver's BER denominators are A (early stop) / K (MaxBlock), :185,196
         res = run_point(src, decoder.decode_batch, decoder.K, eb, batch, max_blocks, stop_blkerrs, A=decoder.out_bits,
