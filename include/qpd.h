@@ -98,7 +98,8 @@ enum qpd_status {
     QPD_E_INPUT = -4        /* input the reference cannot decode defined-ly,
                                seen on device: a channel symbol outside
                                [0, v); a Lloyd index outside the
-                               reconstruction list; a NaN path metric       */
+                               reconstruction list; a NaN path metric; a NaN
+                               LLR given to the channel quantizer           */
 };
 
 /*
@@ -234,8 +235,8 @@ int qpd_set_host_engine(qpd_decoder *dec, int32_t mode);
 /* Returns QPD_E_INPUT (and clears the flags) if any decode since the last
  * check saw a channel symbol outside [0, v), a Lloyd bisect index outside
  * the reconstruction list, or a NaN path metric reaching a list selection
- * (each undefined behaviour in the reference); waits for the decoder's
- * previous work (not the whole device). */
+ * (each undefined behaviour in the reference), or a NaN LLR in qpd_quantize_llr /
+ * qpd_decode_llr; waits for the decoder's previous work (not the whole device). */
 int qpd_check_input_error(qpd_decoder *dec);
 
 /*
@@ -297,6 +298,41 @@ int qpd_mc_llr(qpd_decoder *dec, const qpd_mc_channel *ch, const double *rec, ui
  * generated, then decoded, then the counters over the whole range. */
 int qpd_mc_decode_f64(qpd_decoder *dec, const qpd_mc_channel *ch, const double *rec, uint64_t seed, int64_t frame0,
                       int64_t B, uint8_t *d_msg, uint8_t *d_out, int64_t *d_counts, void *stream);
+
+/*
+ * LLRs on the LUT decoders: the driver's channel quantizer
+ * (mainQuantizedDecoder_LLRDomain.py:167-176) on the device, in front of the
+ * decode -- what qpd_decode_f64 is to the float64-LLR decoders.  ch: the
+ * qpd_mc_channel above; sigma is not read (0 is fine); edges (ascending, n_edges
+ * in 2..257) and lut (values in [0, q)) as for qpd_mc_frames.  Exactly that rule
+ * for every double, +-inf and +-0 included:
+ *     llr <= edges[0] -> 0,  llr >= edges[M] -> q-1,  else lut[bisect_left(edges[:M], llr) - 1];
+ * a float32 LLR is widened to double first (exact).  A NaN has no symbol in the
+ * driver: it is quantized to symbol 0 and raises the decoder's input-error word
+ * (qpd_check_input_error / the host entry point: QPD_E_INPUT, as for a symbol
+ * outside [0, v)); the other frames of the batch are not affected.
+ * d_llr: device float64 or float32 [B][N] (llr_type), 8- / 4-byte aligned
+ * (QPD_E_INVALID otherwise); 16-byte alignment is the fast case.  LUT kinds only
+ * (QPD_E_INVALID for a float64-LLR decoder: use qpd_decode_f64).  Stream
+ * ordering, the per-handle lock and qpd_info.last_engine as for qpd_decode;
+ * qpd_info.u8_staged is 0 after these calls.
+ */
+enum qpd_llr_type { QPD_LLR_F64 = 0, QPD_LLR_F32 = 1 };
+/* The channel quantizer alone: d_symbols, device uint8 [B][N] (q <= 256). */
+int qpd_quantize_llr(qpd_decoder *dec, const qpd_mc_channel *ch, const void *d_llr, int32_t llr_type, int64_t B,
+                     uint8_t *d_symbols, void *stream);
+/* Quantize + decode: d_out = what qpd_decode_u8 returns for qpd_quantize_llr's
+ * symbols (q <= v).  A fast-engine decoder in pre-mode never sees the symbols:
+ * the quantizer writes the root pre-pass rows the decode kernel reads, chunk by
+ * chunk (one front launch per chunk, timed as QPD_KC_PRE); every other decoder
+ * gets int32 symbols in the staging buffer qpd_decode_u8 uses. */
+int qpd_decode_llr(qpd_decoder *dec, const qpd_mc_channel *ch, const void *d_llr, int32_t llr_type, int64_t B,
+                   uint8_t *d_out, void *stream);
+/* The same from host buffers, synchronous: the LLRs are quantized on the host
+ * (the same function), then as qpd_decode_u8_host -- the host engine up to
+ * qpd_info.host_max_frames frames, the GPU above, qpd_set_host_engine honoured. */
+int qpd_decode_llr_host(qpd_decoder *dec, const qpd_mc_channel *ch, const void *h_llr, int32_t llr_type, int64_t B,
+                        uint8_t *h_out);
 
 /*
  * Offline table design (host code, no device needed) -- the reference's
@@ -374,7 +410,7 @@ int qpd_get_info(const qpd_decoder *dec, qpd_info *info);
  * call, then forgets them.  Arrays have QPD_KC_COUNT entries.
  */
 enum qpd_kernel_class {
-    QPD_KC_PRE = 0,    /* root_pre_kernel (fast engine, root pre-pass)              */
+    QPD_KC_PRE = 0,    /* root_pre_kernel (fast engine, root pre-pass); llr_front_kernel (the LLR calls) */
     QPD_KC_DECODE = 1, /* lut_fast_kernel / generic_decode_kernel                   */
     QPD_KC_MC = 2,     /* mc_frames_kernel (qpd_mc_frames, qpd_mc_llr, both fused calls) */
     QPD_KC_PFX = 3,    /* lut_prefix_kernel (fast engine, frozen prefix of list kinds) */

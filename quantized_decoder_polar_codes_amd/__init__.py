@@ -11,6 +11,7 @@ from . import codes, lut  # noqa: F401
 from .decoders import (  # noqa: F401
     CAFastSCLLUTDecoder,
     CASCLLUTDecoder,
+    ChannelQuantizer,
     FastSCLLUTDecoder,
     FastSCLUTDecoder,
     SCDecoder,

@@ -40,6 +40,9 @@ EXPORTED = (
     "qpd_mc_decode",
     "qpd_mc_llr",
     "qpd_mc_decode_f64",
+    "qpd_quantize_llr",
+    "qpd_decode_llr",
+    "qpd_decode_llr_host",
     "qpd_optls_quantizer",
     "qpd_lutgen_mindistortion",
     "qpd_profile",
@@ -51,6 +54,7 @@ QPD_KC_PRE, QPD_KC_DECODE, QPD_KC_MC, QPD_KC_PFX, QPD_KC_COUNT = range(5)
 QPD_PROBE_BPERMUTE, QPD_PROBE_READ_B32, QPD_PROBE_READ_B64 = range(3)
 QPD_HOST_AUTO, QPD_HOST_GPU, QPD_HOST_CPU = range(3)
 QPD_RAN_NONE, QPD_RAN_GPU, QPD_RAN_HOST = range(3)
+QPD_LLR_F64, QPD_LLR_F32 = range(2)
 
 _P = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -188,6 +192,12 @@ def load():
     L.qpd_mc_llr.restype = ctypes.c_int
     L.qpd_mc_decode_f64.argtypes = [_P, ctypes.POINTER(QpdMcChannel), _P, ctypes.c_uint64, _i64, _i64, _P, _P, _P, _P]
     L.qpd_mc_decode_f64.restype = ctypes.c_int
+    L.qpd_quantize_llr.argtypes = [_P, ctypes.POINTER(QpdMcChannel), _P, _i32, _i64, _P, _P]
+    L.qpd_quantize_llr.restype = ctypes.c_int
+    L.qpd_decode_llr.argtypes = [_P, ctypes.POINTER(QpdMcChannel), _P, _i32, _i64, _P, _P]
+    L.qpd_decode_llr.restype = ctypes.c_int
+    L.qpd_decode_llr_host.argtypes = [_P, ctypes.POINTER(QpdMcChannel), _P, _i32, _i64, _P]
+    L.qpd_decode_llr_host.restype = ctypes.c_int
     L.qpd_optls_quantizer.argtypes = [_P, _P, _i32, _i32, _i32, _P, _P, _P, _P]
     L.qpd_optls_quantizer.restype = ctypes.c_int
     L.qpd_lutgen_mindistortion.argtypes = [_i32, _i32, _P, _P, _i32, _i32, _P, _P, _P, _P]

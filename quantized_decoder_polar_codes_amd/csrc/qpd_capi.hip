@@ -3,8 +3,9 @@
 // (qpd_decoder.hpp), qpd_create's decisions (qpd_config.hpp) and steps
 // (qpd_capi_build.hpp), the device-buffer decodes (qpd_capi_decode.hpp), the
 // host-buffer ones (qpd_capi_host.hpp), the Monte-Carlo front end
-// (qpd_capi_mc.hpp).  Host code only; this unit also compiles the small
-// kernels (root pre-pass, widening copy, Monte-Carlo, LDS probe); the decode
+// (qpd_capi_mc.hpp), the LLR front end (qpd_capi_llr.hpp).  Host code only; this
+// unit also compiles the small kernels (root pre-pass, widening copy,
+// Monte-Carlo, LLR quantizer, LDS probe); the decode
 // kernels are in qpd_generic.hip / qpd_fast.hip and their units.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,7 @@
 #include "qpd_fast_plan.hpp"
 #include "qpd_fast_pre.hpp"
 #include "qpd_mc.hip"
+#include "qpd_llr.hip"
 #include "qpd_probe.hip"
 
 #include "qpd_decoder.hpp"
@@ -20,6 +22,7 @@
 #include "qpd_capi_decode.hpp"
 #include "qpd_capi_host.hpp"
 #include "qpd_capi_mc.hpp"
+#include "qpd_capi_llr.hpp"
 
 extern "C" {
 
@@ -146,6 +149,40 @@ int qpd_decode_f64_host(qpd_decoder *d, const double *h_llr, int64_t B, uint8_t 
     if (!run) return rc;
     return host_decode(d, d->heng_f64.get(), h_llr, B, h_out,
                        [&](const double *in, uint8_t *out, hipStream_t st) { return decode_f64_impl(d, in, B, out, st); });
+}
+
+int qpd_quantize_llr(qpd_decoder *d, const qpd_mc_channel *ch, const void *d_llr, int32_t llr_type, int64_t B,
+                     uint8_t *d_symbols, void *stream) {
+    bool run;
+    const int rc = check_llr_args(d, ch, d_llr, llr_type, B, d_symbols, 256, "qpd_quantize_llr: q must be at most 256", &run);
+    if (!run) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return ordered(d, st, [&]() { return llr_front(d, llr_front_args(d, ch), d_llr, llr_type, B, d_symbols, qpd::LLR_U8, st); });
+}
+
+int qpd_decode_llr(qpd_decoder *d, const qpd_mc_channel *ch, const void *d_llr, int32_t llr_type, int64_t B,
+                   uint8_t *d_out, void *stream) {
+    bool run;
+    const int rc = check_llr_args(d, ch, d_llr, llr_type, B, d_out, -1, "qpd_decode_llr: q must be at most the decoder's v", &run);
+    if (!run) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return ordered(d, st, [&]() { return decode_llr_impl(d, ch, d_llr, llr_type, B, d_out, st); });
+}
+
+int qpd_decode_llr_host(qpd_decoder *d, const qpd_mc_channel *ch, const void *h_llr, int32_t llr_type, int64_t B,
+                        uint8_t *h_out) {
+    bool run;
+    int rc = check_llr_args(d, ch, h_llr, llr_type, B, h_out, -1, "qpd_decode_llr_host: q must be at most the decoder's v", &run);
+    if (!run) return rc;
+    std::vector<uint8_t> sym((size_t)B * d->N);
+    const int32_t flag = llr_type == QPD_LLR_F32 ? quantize_llr_host(ch, (const float *)h_llr, B * d->N, sym.data())
+                                                 : quantize_llr_host(ch, (const double *)h_llr, B * d->N, sym.data());
+    rc = host_decode(d, d->heng_lut.get(), sym.data(), B, h_out, [&](const uint8_t *in, uint8_t *out, hipStream_t st) {
+        const int r = decode_u8_impl(d, in, B, out, st);
+        d->u8_staged = 0;  // the staging is this call's own business: qpd_info.u8_staged is about uint8 input
+        return r;
+    });
+    return rc ? rc : flag ? input_error(flag) : QPD_OK;
 }
 
 int qpd_set_host_engine(qpd_decoder *d, int32_t mode) {

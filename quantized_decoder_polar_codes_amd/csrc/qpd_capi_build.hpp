@@ -114,6 +114,7 @@ int configure(qpd_decoder *d, const qpd_config *cfg, int fam, int n, int dom) {
     if (engine < 0) return fail(engine, err);
     d->engine = engine;
     if (const char *e = getenv("QPD_U8_CHUNK")) d->u8_chunk = std::max<int64_t>(1, atoll(e));
+    if (const char *e = getenv("QPD_LLR_COOP")) d->llr_coop = atoi(e) != 0;
     return QPD_OK;
 }
 

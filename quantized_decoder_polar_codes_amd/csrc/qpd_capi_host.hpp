@@ -13,6 +13,7 @@ int input_error(int32_t flag) {
     if (flag & qpd::ERR_SYMBOL) msg += "channel symbol outside [0, v) in decoder input; ";
     if (flag & qpd::ERR_LLOYD) msg += "Lloyd bisect index outside the reconstruction list (reference UB); ";
     if (flag & qpd::ERR_NAN_PM) msg += "NaN path metric reached the list sort (reference UB); ";
+    if (flag & qpd::ERR_NAN_LLR) msg += "NaN LLR in decoder input (no channel symbol in the reference driver); ";
     msg.resize(msg.size() - 2);
     return fail(QPD_E_INPUT, msg);
 }

@@ -103,9 +103,10 @@ struct qpd_decoder {
     DeviceChunk mc_llr;       // qpd_mc_decode_f64: float64 LLRs of one chunk (qpd_chunk.hpp: mc_llr_chunk_frames)
     DeviceBuf mc_rec;         // qpd_mc_llr / qpd_mc_decode_f64 with rec: the reconstruction table's device copy
     std::vector<double> mc_rec_host;  // what mc_rec holds (empty: nothing)
-    DeviceChunk u8_sym;       // qpd_decode_u8 outside pre-mode: int32 symbols of one chunk (widen_u8_kernel)
+    DeviceChunk u8_sym;       // qpd_decode_u8 / qpd_decode_llr outside pre-mode: int32 symbols of one chunk
     int64_t u8_chunk = 0;    // QPD_U8_CHUNK (tests): frames per staging chunk (0: 1 GB of int32 symbols)
     int u8_staged = 0;       // qpd_info.u8_staged: the last decode call widened its input into u8_sym
+    bool llr_coop = true;    // qpd_decode_llr in pre-mode: the front kernel's cooperative read (QPD_LLR_COOP=0: per owner)
     DevPlan plan{};
     qpd::FastPlan fplan{};
     DeviceBuf f_tab, g_tab, fscratch, mops, r1_rank, task_ctr;

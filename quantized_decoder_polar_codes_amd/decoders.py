@@ -31,7 +31,7 @@ from . import _lib
 from .lut import PackedLUT, pack_luts
 from .quant import LloydQuant, UniformQuant, pack_lloyd, pack_uniform
 
-__all__ = ["SCDecoder", "SCLUTDecoder", "SCLLUTDecoder", "FastSCLUTDecoder", "FastSCLLUTDecoder",
+__all__ = ["ChannelQuantizer", "SCDecoder", "SCLUTDecoder", "SCLLUTDecoder", "FastSCLUTDecoder", "FastSCLLUTDecoder",
            "CASCLLUTDecoder", "CAFastSCLLUTDecoder", "SCLDecoder", "CASCLDecoder", "FastSCDecoder", "FastSCLDecoder",
            "SCUniformQuantizedDecoder", "SCLUniformQuantizedDecoder", "SCLloydQuantizedDecoder",
            "SCLLloydQuantizedDecoder"]
@@ -57,6 +57,59 @@ def _torch():
         return torch
     except Exception:  # pragma: no cover - torch is part of the image
         return None
+
+
+class ChannelQuantizer:
+    """The drivers' channel quantizer as a value (mainQuantizedDecoder_LLRDomain.py:135-145,
+    :167-176): ``edges`` (interval_x, ascending, 2..257 of them), ``lut`` (channel_lut, one entry in
+    [0, q) per bin) and ``q`` channel symbols -- what ``lutgen.channel_quantizer`` (its
+    interval_x and channel_lut), ``lutgen.design`` (the same call at the design's sigma) and
+    ``montecarlo.uniform_channel_quantizer`` return.  Validated once; keeps the arrays the C
+    struct points to alive.  ``decode_llr_batch`` / ``quantize_llr`` of the LUT decoders take it."""
+
+    def __init__(self, edges, lut, q: int | None = None):
+        self.edges = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+        lut = np.asarray(lut).reshape(-1)
+        self.lut = np.ascontiguousarray(lut.astype(np.int32))
+        if not 2 <= self.edges.size <= 257:
+            raise ValueError(f"a channel quantizer has 2..257 edges, got {self.edges.size}")
+        if self.lut.size != self.edges.size - 1 or not (self.lut == lut).all():
+            raise ValueError(f"lut must have one integer per bin ({self.edges.size - 1}), got {lut.size} entries")
+        if not (self.edges[:-1] <= self.edges[1:]).all():  # a NaN edge fails it too
+            raise ValueError("edges must be ascending")
+        self.q = int(self.lut.max()) + 1 if q is None else int(q)
+        if self.q < 2 or self.lut.min() < 0 or self.lut.max() >= self.q:
+            raise ValueError(f"lut entries must be in [0, q) with q >= 2 (q = {self.q})")
+        self.ch = _lib.QpdMcChannel()
+        self.ch.sigma = 0.0  # not read by the LLR entry points
+        self.ch.q, self.ch.n_edges = self.q, self.edges.size
+        self.ch.edges, self.ch.lut = self.edges.ctypes.data, self.lut.ctypes.data
+
+    @classmethod
+    def uniform(cls, v: int = 16, delta: float = 0.5):
+        """montecarlo.uniform_channel_quantizer(v, delta)."""
+        from .montecarlo import uniform_channel_quantizer
+
+        return cls(*uniform_channel_quantizer(v, delta), q=v)
+
+    @classmethod
+    def mindistortion(cls, sigma: float, q_uniform: int = 128, q: int = 16, sum_order: str = "cpp"):
+        """lutgen.channel_quantizer(sigma, q_uniform, q): the drivers' design for AWGN std sigma."""
+        from .lutgen import channel_quantizer
+
+        _, _, edges, lut = channel_quantizer(sigma, q_uniform, q, sum_order)
+        return cls(edges, lut, q=q)
+
+    @classmethod
+    def for_design(cls, design, q_uniform: int = 128, sum_order: str = "cpp"):
+        """The channel quantizer a ``lutgen.design`` result was designed with (its design SNR and v)."""
+        return cls.mindistortion(float(np.sqrt(1 / 10 ** (design.design_snr_db / 10))), q_uniform, design.v, sum_order)
+
+    def __call__(self, llr) -> np.ndarray:
+        """The symbols on the host (codes.quantize_channel)."""
+        from .codes import quantize_channel
+
+        return quantize_channel(llr, self.edges, self.lut, self.q)
 
 
 class _DecoderBase:
@@ -159,7 +212,7 @@ class _DecoderBase:
 
     def kernel_times(self) -> dict:
         """{class: (ms summed, launches)} since the last call, for the classes
-        'pre' (root pre-pass), 'decode', 'mc' (frame generator) and 'pfx'
+        'pre' (root pre-pass, or the LLR calls' quantizer), 'decode', 'mc' (frame generator) and 'pfx'
         (frozen prefix, lut_prefix_kernel)."""
         ms = (ctypes.c_double * _lib.QPD_KC_COUNT)()
         n = (ctypes.c_int64 * _lib.QPD_KC_COUNT)()
@@ -198,6 +251,68 @@ class _DecoderBase:
         out = np.empty((B, self.out_bits), dtype=np.uint8)
         fn = lib.qpd_decode_f64_host if self._float_input else lib.qpd_decode_u8_host if u8 else lib.qpd_decode_host
         _lib.check(fn(self._h, _ptr(a), B, _ptr(out)))
+        return out
+
+    # -- LLR input of the LUT decoders ------------------------------------------
+    def _llr_args(self, llr, quantizer, name):
+        """(device?, contiguous [B, N] array / tensor, llr_type) of an LLR batch."""
+        if self._float_input:
+            raise TypeError(f"{type(self).__name__} decodes float64 LLRs as they are: use decode_batch, not {name}")
+        if not isinstance(quantizer, ChannelQuantizer):
+            raise TypeError(f"{name} takes a ChannelQuantizer, got {type(quantizer).__name__}")
+        torch = _torch()
+        if torch is not None and isinstance(llr, torch.Tensor) and llr.is_cuda:
+            if not llr.dtype.is_floating_point:
+                raise TypeError(f"{name} takes floating-point LLRs, got {llr.dtype}")
+            want = llr.dtype if llr.dtype in (torch.float64, torch.float32) else torch.float64
+            xs = llr.reshape(-1, self.N).to(want).contiguous()
+            return True, xs, _lib.QPD_LLR_F32 if want == torch.float32 else _lib.QPD_LLR_F64
+        if torch is not None and isinstance(llr, torch.Tensor):
+            llr = llr.numpy()
+        a = np.asarray(llr)
+        if a.dtype.kind != "f":
+            raise TypeError(f"{name} takes floating-point LLRs, got {a.dtype}")
+        want = a.dtype if a.dtype in (np.float64, np.float32) else np.float64
+        a = np.ascontiguousarray(a.astype(want, copy=False).reshape(-1, self.N))
+        return False, a, _lib.QPD_LLR_F32 if want == np.float32 else _lib.QPD_LLR_F64
+
+    def decode_llr_batch(self, llr, quantizer: "ChannelQuantizer"):
+        """Decode B frames of channel LLRs on a LUT decoder: ``quantizer`` (the drivers'
+        channel quantizer, q <= v) runs in front of the decode, in the library.  A torch
+        CUDA float64 / float32 tensor [B, N] is read where it is (qpd_decode_llr on the
+        current stream, no copy) -> torch CUDA uint8 [B, K]; other float dtypes are
+        converted to float64; a numpy array goes to qpd_decode_llr_host -> numpy uint8
+        [B, K].  The bits are decode_batch's for ``quantizer(llr)``.  A NaN LLR raises
+        ValueError (numpy), or is reported by qpd_check_input_error (device)."""
+        dev, xs, ty = self._llr_args(llr, quantizer, "decode_llr_batch")
+        lib = _lib.load()
+        B = xs.shape[0]
+        if dev:
+            torch = _torch()
+            out = torch.empty((B, self.out_bits), dtype=torch.uint8, device=xs.device)
+            stream = torch.cuda.current_stream(xs.device).cuda_stream
+            _lib.check(lib.qpd_decode_llr(self._h, ctypes.byref(quantizer.ch), ctypes.c_void_p(xs.data_ptr()), ty, B,
+                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)))
+            return out
+        out = np.empty((B, self.out_bits), dtype=np.uint8)
+        _lib.check(lib.qpd_decode_llr_host(self._h, ctypes.byref(quantizer.ch), _ptr(xs), ty, B, _ptr(out)))
+        return out
+
+    def quantize_llr(self, llr, quantizer: "ChannelQuantizer"):
+        """The channel quantizer alone (q <= 256): a torch CUDA tensor [B, N] ->
+        torch CUDA uint8 symbols [B, N] on the current stream (qpd_quantize_llr); a
+        numpy array -> numpy uint8, through the device."""
+        dev, xs, ty = self._llr_args(llr, quantizer, "quantize_llr")
+        torch = _torch()
+        if not dev:
+            if torch is None:
+                raise RuntimeError("quantize_llr runs on the device: it needs torch")
+            return self.quantize_llr(torch.from_numpy(xs).to(torch.device("cuda", max(self.device, 0))),
+                                     quantizer).cpu().numpy()
+        out = torch.empty(xs.shape, dtype=torch.uint8, device=xs.device)
+        stream = torch.cuda.current_stream(xs.device).cuda_stream
+        _lib.check(_lib.load().qpd_quantize_llr(self._h, ctypes.byref(quantizer.ch), ctypes.c_void_p(xs.data_ptr()), ty,
+                                                xs.shape[0], ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)))
         return out
 
     def set_host_engine(self, mode: str = "auto") -> None:
