@@ -232,6 +232,60 @@ int qpd_decode_f64_host(qpd_decoder *dec, const double *h_llr, int64_t B, uint8_
 enum qpd_host_mode { QPD_HOST_AUTO = 0, QPD_HOST_GPU = 1, QPD_HOST_CPU = 2 };
 int qpd_set_host_engine(qpd_decoder *dec, int32_t mode);
 
+/*
+ * Decode with status: what a receiver needs besides the bits of a list decode --
+ * the path metric of the output path and, for the CRC-aided kinds, whether that
+ * path passed the CRC -- and an optional mask on the CRC (the RNTI of PDCCH blind
+ * detection).  The counterpart of the reference's float CA-SCL with RNTI,
+ *     CASCL::decode(llr, RNTI) -> (bits, PM, isPass)
+ *         PolarEncoder/PolarBD/_cpp/src/CASCLWithRNTI.cpp:74-252
+ * (the mask at :222-224, the return value at :252; CASCLDecoder.cpp:202-234
+ * computes the same PM and isPass and drops them), for every list kind here.
+ *
+ * in_type says what d_in holds: int32 symbols (as qpd_decode), uint8 symbols
+ * (qpd_decode_u8) or float64 LLRs (qpd_decode_f64); it must fit the decoder
+ * (QPD_E_INVALID otherwise).  st == NULL, or no mask and both outputs NULL:
+ * exactly that call.  With crc_mask_bits == 0 the output bits are always that
+ * call's.  Stream ordering, the per-handle lock, the error word and
+ * qpd_info.last_engine / u8_staged as for those calls; the host variant keeps
+ * their host_max_frames dispatch (qpd_set_host_engine honoured).
+ *
+ * metric, crc_pass: device pointers in qpd_decode_status, host pointers in
+ * qpd_decode_status_host; each may be NULL.  crc_mask: always a host pointer,
+ * read before the call returns.  Frames >= B are never written.
+ *   metric[f]   the final path metric (the decoder's own PML double) of the path
+ *               whose bits are output.  List kinds only, CRC-aided or not, on
+ *               every engine; QPD_E_INVALID for the SC / FastSC kinds.
+ *   crc_pass[f] CRC-aided kinds only (QPD_E_INVALID otherwise): 1 iff the output
+ *               path is the first path, in argsort(PML) order, whose CRC compare
+ *               succeeded (the reference's isPass; the compare is the one of
+ *               qpd_config.A above: K - A bits for the LUT kinds, crc_n bits for
+ *               QPD_CASCL_FLOAT); 0: none did, the output is the best-metric path.
+ *   crc_mask    crc_mask_bits entries of 0 / 1; bit l is XORed onto check-code bit
+ *               crc_n - crc_mask_bits + l before the compare, so it changes which
+ *               path wins.  crc_mask_bits > crc_n (the reference writes out of
+ *               bounds there), or any mask bits on a kind without CRC:
+ *               QPD_E_INVALID.
+ * A list of one path (L = 1) has no selection to report: QPD_E_UNSUPPORTED when
+ * metric or crc_pass is asked for.
+ * Deviation from the reference: it returns PML[i], i the winner's position in
+ * the argsort order, not the winner's index (CASCLWithRNTI.cpp:234) -- the
+ * winner's metric only while the final PML is ascending, which mink guarantees
+ * when the code's last position is an information bit.  metric[f] here is
+ * always the output path's own metric.
+ */
+enum qpd_input_type { QPD_IN_I32 = 0, QPD_IN_U8 = 1, QPD_IN_F64 = 2 };
+typedef struct qpd_status_args {
+    const uint8_t *crc_mask;   /* host, [crc_mask_bits] of 0/1, or NULL          */
+    int32_t crc_mask_bits;     /* 0..crc_n                                        */
+    double  *metric;           /* [B] or NULL: path metric of the output path     */
+    uint8_t *crc_pass;         /* [B] or NULL: 1 = the output path passed the CRC */
+} qpd_status_args;
+int qpd_decode_status(qpd_decoder *dec, const void *d_in, int32_t in_type, int64_t B, uint8_t *d_out,
+                      const qpd_status_args *st, void *stream);
+int qpd_decode_status_host(qpd_decoder *dec, const void *h_in, int32_t in_type, int64_t B, uint8_t *h_out,
+                           const qpd_status_args *st);
+
 /* Returns QPD_E_INPUT (and clears the flags) if any decode since the last
  * check saw a channel symbol outside [0, v), a Lloyd bisect index outside
  * the reconstruction list, or a NaN path metric reaching a list selection

@@ -49,12 +49,15 @@ EXPORTED = (
     "qpd_kernel_times",
     "qpd_probe_lds",
     "qpd_set_host_engine",
+    "qpd_decode_status",
+    "qpd_decode_status_host",
 )
 QPD_KC_PRE, QPD_KC_DECODE, QPD_KC_MC, QPD_KC_PFX, QPD_KC_COUNT = range(5)
 QPD_PROBE_BPERMUTE, QPD_PROBE_READ_B32, QPD_PROBE_READ_B64 = range(3)
 QPD_HOST_AUTO, QPD_HOST_GPU, QPD_HOST_CPU = range(3)
 QPD_RAN_NONE, QPD_RAN_GPU, QPD_RAN_HOST = range(3)
 QPD_LLR_F64, QPD_LLR_F32 = range(2)
+QPD_IN_I32, QPD_IN_U8, QPD_IN_F64 = range(3)
 
 _P = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -107,6 +110,15 @@ class QpdMcChannel(ctypes.Structure):
         ("n_edges", _i32),
         ("edges", _P),
         ("lut", _P),
+    ]
+
+
+class QpdStatusArgs(ctypes.Structure):
+    _fields_ = [
+        ("crc_mask", _P),
+        ("crc_mask_bits", _i32),
+        ("metric", _P),
+        ("crc_pass", _P),
     ]
 
 
@@ -210,6 +222,12 @@ def load():
     L.qpd_probe_lds.restype = ctypes.c_int
     L.qpd_set_host_engine.argtypes = [_P, _i32]
     L.qpd_set_host_engine.restype = ctypes.c_int
+    # (QPD_LIB may name an older diagnostic build of the same ABI, e.g. the parent in an A/B run)
+    if not os.environ.get("QPD_LIB") or hasattr(L, "qpd_decode_status"):
+        L.qpd_decode_status.argtypes = [_P, _P, _i32, _i64, _P, ctypes.POINTER(QpdStatusArgs), _P]
+        L.qpd_decode_status.restype = ctypes.c_int
+        L.qpd_decode_status_host.argtypes = [_P, _P, _i32, _i64, _P, ctypes.POINTER(QpdStatusArgs)]
+        L.qpd_decode_status_host.restype = ctypes.c_int
     if L.qpd_abi_version() != ABI_VERSION:
         raise ImportError("libqpd.so ABI version mismatch")
     L.qpd_build_id.restype = ctypes.c_char_p

@@ -30,6 +30,12 @@ UNITS = [
     ("qpd_fast_fscl.hip", []),
     ("qpd_fast_fscl1.hip", []),
     ("qpd_fast_fscl16.hip", []),
+    # the same list-kind kernels with the decode-status tail (qpd_decode_status)
+    ("qpd_k_scl_st.hip", []),
+    ("qpd_k_scl1_st.hip", []),
+    ("qpd_fast_fscl_st.hip", []),
+    ("qpd_fast_fscl1_st.hip", []),
+    ("qpd_fast_fscl16_st.hip", []),
     ("qpd_k_generic.hip", []),
     ("qpd_lutgen.cpp", []),
 ]

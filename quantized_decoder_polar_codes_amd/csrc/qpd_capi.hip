@@ -24,6 +24,50 @@
 #include "qpd_capi_mc.hpp"
 #include "qpd_capi_llr.hpp"
 
+namespace {
+
+// The checks of both status entry points: the request, then the decode's own.
+int check_status_call(const qpd_decoder *d, int32_t in_type, const qpd_status_args *sa, const char *suffix,
+                             int64_t B, const void *in, const void *out, qpd_stat::Req *rq, bool *run) {
+    *run = false;
+    if (!d) return fail(QPD_E_INVALID, "null decoder");
+    std::string err;
+    const int rc = qpd_stat::check(d->pub_kind, d->L, d->crc_n, in_type, sa, rq, err);
+    if (rc) return fail(rc, err);
+    return check_decode_args(d, in_type != QPD_IN_F64, suffix, B, in, out, run);
+}
+
+template <class Eng, class In>
+int status_host(qpd_decoder *d, Eng *eng, const In *h_in, int32_t in_type, int64_t B, uint8_t *h_out,
+                       const qpd_stat::Req &rq) {
+    if (host_engine_takes(d, B)) {
+        std::lock_guard<std::mutex> lk(d->mu);
+        d->last_engine = QPD_RAN_HOST;
+        d->u8_staged = 0;
+        const int32_t flag = qpd_stat::host_run(eng, h_in, B, d->N, d->out_bits, h_out, rq);
+        return flag ? input_error(flag) : QPD_OK;
+    }
+    // the GPU: metrics and flags through a device buffer of the handle, copied back on
+    // its stream before host_roundtrip's synchronization
+    return host_roundtrip(d, h_in, B, h_out, [&](const In *in, uint8_t *out, hipStream_t hs) -> int {
+        int rc = ensure(d->h_st, d->h_st_bytes, (size_t)B * 9);
+        if (rc) return rc;
+        qpd_stat::Req dev = rq;
+        if (rq.metric) dev.metric = (double *)d->h_st.p;
+        if (rq.pass) dev.pass = (uint8_t *)d->h_st.p + (size_t)B * 8;
+        {
+            StatusScope sc(d, dev, out);
+            rc = decode_typed(d, in, in_type, B, out, hs);
+        }
+        if (rc) return rc;
+        if (rq.metric) QPD_HIP(hipMemcpyAsync(rq.metric, dev.metric, (size_t)B * 8, hipMemcpyDeviceToHost, hs));
+        if (rq.pass) QPD_HIP(hipMemcpyAsync(rq.pass, dev.pass, (size_t)B, hipMemcpyDeviceToHost, hs));
+        return QPD_OK;
+    });
+}
+
+}  // namespace
+
 extern "C" {
 
 int qpd_abi_version(void) { return QPD_ABI_VERSION; }
@@ -114,6 +158,32 @@ int qpd_decode_f64(qpd_decoder *d, const double *d_llr, int64_t B, uint8_t *d_ou
     if (!run) return rc;
     hipStream_t st = (hipStream_t)stream;
     return ordered(d, st, [&]() { return decode_f64_impl(d, d_llr, B, d_out, st); });
+}
+
+int qpd_decode_status(qpd_decoder *d, const void *d_in, int32_t in_type, int64_t B, uint8_t *d_out,
+                      const qpd_status_args *sa, void *stream) {
+    bool run;
+    qpd_stat::Req rq;
+    const int rc = check_status_call(d, in_type, sa, "", B, d_in, d_out, &rq, &run);
+    if (!run) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return ordered(d, st, [&]() {
+        StatusScope sc(d, rq, d_out);
+        return decode_typed(d, d_in, in_type, B, d_out, st);
+    });
+}
+
+int qpd_decode_status_host(qpd_decoder *d, const void *h_in, int32_t in_type, int64_t B, uint8_t *h_out,
+                           const qpd_status_args *sa) {
+    bool run;
+    qpd_stat::Req rq;
+    const int rc = check_status_call(d, in_type, sa, "_host", B, h_in, h_out, &rq, &run);
+    if (!run) return rc;
+    switch (in_type) {
+        case QPD_IN_I32: return status_host(d, d->heng_lut.get(), (const int32_t *)h_in, in_type, B, h_out, rq);
+        case QPD_IN_U8: return status_host(d, d->heng_lut.get(), (const uint8_t *)h_in, in_type, B, h_out, rq);
+        default: return status_host(d, d->heng_f64.get(), (const double *)h_in, in_type, B, h_out, rq);
+    }
 }
 
 int qpd_check_input_error(qpd_decoder *d) {

@@ -24,6 +24,12 @@ const void *fast_kernel_fscl(int sets, bool l8, bool r1l);       // qpd_fast_fsc
 const void *fast_kernel_fscl_pw1(int sets, bool l8, bool r1l);   // qpd_fast_fscl1.hip
 const void *fast_kernel_fscl_w16(int sets, bool pw1);            // qpd_fast_fscl16.hip
 const void *generic_kernel(int fam, int dom, bool wide);         // qpd_k_generic.hip
+// the list kinds' decode-status instantiations (ST), one unit per unit above (*_st.hip)
+const void *fast_kernel_scl_st(int sets, bool l8, bool w16);
+const void *fast_kernel_scl_pw1_st(int sets, bool l8, bool w16);
+const void *fast_kernel_fscl_st(int sets, bool l8, bool r1l);
+const void *fast_kernel_fscl_pw1_st(int sets, bool l8, bool r1l);
+const void *fast_kernel_fscl_w16_st(int sets, bool pw1);
 }  // namespace qpd
 
 namespace {
@@ -32,7 +38,17 @@ using qpd_sched::Schedule;
 
 // The decode kernel instantiation of a plan (nullptr: none, the launch fails).
 // pw1: the op list's pointer fields fit one word (compact_pointer_fields).
-const void *fast_kernel(int kind, int sets, bool l8, bool r1l, bool pw1, bool w16) {
+const void *fast_kernel(int kind, int sets, bool l8, bool r1l, bool pw1, bool w16, bool st = false) {
+    if (st) {  // the same plan's kernel with the decode-status tail (list kinds)
+        switch (kind) {
+            case QPD_SCL_LUT:
+                return r1l ? nullptr : pw1 ? qpd::fast_kernel_scl_pw1_st(sets, l8, w16) : qpd::fast_kernel_scl_st(sets, l8, w16);
+            case QPD_FASTSCL_LUT:
+                if (w16) return r1l ? nullptr : qpd::fast_kernel_fscl_w16_st(sets, pw1);
+                return pw1 ? qpd::fast_kernel_fscl_pw1_st(sets, l8, r1l) : qpd::fast_kernel_fscl_st(sets, l8, r1l);
+            default: return nullptr;
+        }
+    }
     switch (kind) {
         case QPD_SC_LUT:
         case QPD_FASTSC_LUT: return pw1 || r1l ? nullptr : qpd::fast_kernel_single(kind, sets);
@@ -265,6 +281,11 @@ int build_fast(qpd_decoder *d, const qpd_config *c, const Schedule &s) {
     const void *kfn = fast_kernel(d->kind, d->sets, d->l8, d->r1l, d->pw1, d->w16);
     if (!kfn) return fail(QPD_E_UNSUPPORTED, "fast plan: no decode kernel instantiation for this plan");
     if ((rc = check_no_static_lds(kfn, "fast decode kernel"))) return rc;
+    if (d->kind == QPD_SCL_LUT || d->kind == QPD_FASTSCL_LUT) {  // qpd_decode_status runs the plan's ST twin
+        const void *ksfn = fast_kernel(d->kind, d->sets, d->l8, d->r1l, d->pw1, d->w16, true);
+        if (!ksfn) return fail(QPD_E_UNSUPPORTED, "fast plan: no decode-status kernel instantiation for this plan");
+        if ((rc = check_no_static_lds(ksfn, "fast decode-status kernel"))) return rc;
+    }
     // (the prefix stages' two-set instantiations do the same offset-0 byte-table lookups)
     if (d->pfx[0].nops > 0 && d->pfx_sets == 2 &&
         (rc = check_no_static_lds(prefix_kernel(d->kind, d->pfx_sets, d->pw1), "fast prefix kernel")))

@@ -52,12 +52,25 @@ int ensure_records(DeviceBuf &b, size_t &cap, int64_t Bc, int rec, int paths) {
     return QPD_OK;
 }
 
+// The status fields of a launch's plan during qpd_decode_status (nothing asked,
+// every other call: zeros): the call's outputs from the launch's first frame on,
+// which follows from where in the call's d_out the launch writes.
+template <class Plan>
+void status_at(const qpd_decoder *d, const uint8_t *out, Plan &P) {
+    const qpd_stat::Req &rq = d->st_req;
+    const int64_t f0 = rq.any() && out ? (out - d->st_out0) / d->out_bits : 0;
+    P.crc_mask = rq.mask;
+    P.st_metric = rq.metric ? rq.metric + f0 : nullptr;
+    P.st_pass = rq.pass ? rq.pass + f0 : nullptr;
+}
+
 template <class In>
 int launch_generic(qpd_decoder *d, const In *in, int64_t B, uint8_t *out, int grid, hipStream_t st) {
     const void *kfn = generic_kernel(d->kind, d->dom, d->L > qpd::kMaxL);
     if (!kfn) return fail(QPD_E_INVALID, "bad kind");
     qpd::DevPlan P = d->plan;
     P.task_base = d->task_base;
+    status_at(d, out, P);
     const In *in_arg = in;
     void *args[] = {&P, &in_arg, &B, &out};
     const int rc = timed_launch(d, QPD_KC_DECODE, st, [&]() -> int {
@@ -75,8 +88,13 @@ int fast_launch(qpd_decoder *d, qpd::FastPlan fp, const int32_t *in, int64_t Bc,
                 bool prefix = false) {
     const int sets = prefix ? d->pfx_sets : d->sets;
     const int64_t tw = (int64_t)fp.fpw * sets;  // frames per wave task
-    const void *kfn = prefix ? prefix_kernel(d->kind, sets, d->pw1) : fast_kernel(d->kind, d->sets, d->l8, d->r1l, d->pw1, d->w16);
+    // a status call's decode launch runs the plan's ST twin (the plain kernels do not read the status fields)
+    const bool status = !prefix && d->st_req.any();
+    const void *kfn = prefix ? prefix_kernel(d->kind, sets, d->pw1)
+                             : fast_kernel(d->kind, d->sets, d->l8, d->r1l, d->pw1, d->w16, status);
     if (!kfn) return fail(QPD_E_INVALID, "bad kind");
+    qpd::FastStatus so{};
+    if (status) status_at(d, out, so);
     const int64_t fgroups = (Bc + tw - 1) / tw;
     int fgrid = (int)std::min<int64_t>(fgroups, d->max_waves);
     if (!QPD_DYN) {
@@ -86,7 +104,7 @@ int fast_launch(qpd_decoder *d, qpd::FastPlan fp, const int32_t *in, int64_t Bc,
     }
     const qpd::MOp *ops_arg = fp.ops;
     fp.task_base = d->task_base;
-    void *args[] = {&fp, &in, &Bc, &out, &ops_arg};
+    void *args[] = {&fp, &in, &Bc, &out, &ops_arg, &so};
     // the prefix stages run pfx_sets frame sets per wave in the same per-set layout
     const size_t lds = (size_t)((d->lds_bytes - d->lds_tab_bytes) / d->sets * sets + d->lds_tab_bytes);
     const int rc = timed_launch(d, prefix ? QPD_KC_PFX : QPD_KC_DECODE, st, [&]() -> int {
@@ -243,5 +261,27 @@ int check_decode_args(const qpd_decoder *d, bool lut, const char *suffix, int64_
     *run = true;
     return QPD_OK;
 }
+
+// One device-buffer decode by input type (qpd_decode_status; caller as above).
+int decode_typed(qpd_decoder *d, const void *d_in, int32_t in_type, int64_t B, uint8_t *d_out, hipStream_t st) {
+    switch (in_type) {
+        case QPD_IN_I32: return decode_impl(d, (const int32_t *)d_in, B, d_out, st);
+        case QPD_IN_U8: return decode_u8_impl(d, (const uint8_t *)d_in, B, d_out, st);
+        default: return decode_f64_impl(d, (const double *)d_in, B, d_out, st);
+    }
+}
+
+// The status request of a call, held by the handle while its launches are made.
+struct StatusScope {
+    qpd_decoder *d;
+    StatusScope(qpd_decoder *d_, const qpd_stat::Req &rq, const uint8_t *out0) : d(d_) {
+        d->st_req = rq;
+        d->st_out0 = out0;
+    }
+    ~StatusScope() {
+        d->st_req = qpd_stat::Req();
+        d->st_out0 = nullptr;
+    }
+};
 
 }  // namespace

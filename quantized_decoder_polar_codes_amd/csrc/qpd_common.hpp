@@ -226,10 +226,14 @@ __device__ __forceinline__ int stable_rank(double pm, int gl, int gbase, int L) 
     return rank;
 }
 
-// `rank` = this path's position in the argsort(PML) order.
+// `rank` = this path's position in the argsort(PML) order.  `crc_mask`: XORed
+// onto the low bits of the register before the compare (qpd_status_args.crc_mask,
+// CASCLWithRNTI.cpp:222-224; 0: none).  *passed: a path passed the compare -- the
+// output path is the first that did (the reference's isPass).
 template <class WordFn>
 __device__ __forceinline__ int ca_winner_ranked(int rank, int gl, int gbase, int L, int N, const uint32_t *info_mask,
-                                                int A, int chk, int crc_n, uint32_t crc_q, WordFn word) {
+                                                int A, int chk, int crc_n, uint32_t crc_q, WordFn word,
+                                                uint32_t crc_mask, bool *passed) {
     const int K = A + chk;
     const uint32_t top = 1u << (crc_n - 1);
     const uint32_t mask = (top << 1) - 1u;  // crc_n = 32: 0 - 1 = all ones
@@ -249,7 +253,7 @@ __device__ __forceinline__ int ca_winner_ranked(int rank, int gl, int gbase, int
                 const uint32_t fb = bit ^ ((r & top) ? 1u : 0u);
                 r = ((r << 1) & mask) ^ (crc_q & (0u - fb));
             } else {
-                pass = pass && bit == ((r >> (crc_n - 1 - (t - A))) & 1u);
+                pass = pass && bit == (((r ^ crc_mask) >> (crc_n - 1 - (t - A))) & 1u);
             }
             ++t;
         }
@@ -263,13 +267,16 @@ __device__ __forceinline__ int ca_winner_ranked(int rank, int gl, int gbase, int
             best = j;
         }
     }
+    *passed = bk < kMaxLWide;
     return best;
 }
 
 template <class WordFn>
 __device__ __forceinline__ int ca_winner(double pm, int gl, int gbase, int L, int N, const uint32_t *info_mask, int A,
-                                         int chk, int crc_n, uint32_t crc_q, WordFn word) {
-    return ca_winner_ranked(stable_rank(pm, gl, gbase, L), gl, gbase, L, N, info_mask, A, chk, crc_n, crc_q, word);
+                                         int chk, int crc_n, uint32_t crc_q, WordFn word, uint32_t crc_mask,
+                                         bool *passed) {
+    return ca_winner_ranked(stable_rank(pm, gl, gbase, L), gl, gbase, L, N, info_mask, A, chk, crc_n, crc_q, word,
+                            crc_mask, passed);
 }
 
 }  // namespace qpd

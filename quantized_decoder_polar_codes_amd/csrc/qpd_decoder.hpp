@@ -18,6 +18,7 @@
 #include "qpd_fast_plan.hpp"
 #include "qpd_chunk.hpp"
 #include "qpd_host.hpp"
+#include "qpd_status.hpp"
 
 namespace {
 
@@ -130,8 +131,8 @@ struct qpd_decoder {
     DeviceBuf lut_f, f_base, lut_g, g_base, vcl, ops, info_pos, scratch, err;
     DeviceBuf r_f, r_g, q_bnd, q_rec, bnd_off, bnd_len, rec_off, rec_len;  // float-domain re-quantizers
     // staging for the host-buffer entry points
-    DeviceBuf h_in, h_out;
-    size_t h_in_bytes = 0, h_out_bytes = 0;
+    DeviceBuf h_in, h_out, h_st;  // h_st: qpd_decode_status_host's metrics, then its flags
+    size_t h_in_bytes = 0, h_out_bytes = 0, h_st_bytes = 0;
     // The decoder's own stream (created with the handle): every upload of
     // qpd_create, the host-buffer entry points (pinned staging, one stream
     // synchronization per call: copy in, decode, copy out + error word) and
@@ -159,6 +160,11 @@ struct qpd_decoder {
     int host_mode = QPD_HOST_AUTO;
     int64_t host_max_frames = 0;  // QPD_HOST_AUTO: batches up to this size run on the host engine
     int last_engine = QPD_RAN_NONE;  // what served the last decode call (qpd_info.last_engine)
+    // qpd_decode_status, for the length of the call (under `mu`): what its launches
+    // write besides the bits, and the call's d_out -- a chunk's launch finds its
+    // first frame from its own `out` (status_at, qpd_capi_decode.hpp).
+    qpd_stat::Req st_req;
+    const uint8_t *st_out0 = nullptr;
     // qpd_profile: HIP events around every launch, per kernel class
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[QPD_KC_COUNT];

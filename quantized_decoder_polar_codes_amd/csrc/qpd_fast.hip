@@ -30,6 +30,16 @@
 #include "qpd_fast_bot.hpp"
 #include "qpd_fast_special.hpp"
 
+// A unit compiled with QPD_STATUS_UNIT (the *_st.hip wrappers) instantiates the ST
+// kernels and names its lookup function <name>_st.
+#ifdef QPD_STATUS_UNIT
+#define QPD_ST true
+#define QPD_UNIT_FN(f) f##_st
+#else
+#define QPD_ST false
+#define QPD_UNIT_FN(f) f
+#endif
+
 namespace qpd {
 
 // NS frame sets per wave (see qpd_fast_select.hpp); L8: list decoders with L = 8; W16: SCL-LUT and
@@ -48,16 +58,21 @@ namespace qpd {
 // prove the op records are never written and fetch them with scalar loads
 // instead of vector loads + readfirstlane, which drain vmcnt at every op.
 // PW1: one pointer word per path (PathT; the host packed the op list's fields).
-template <int KIND, int NS, bool L8, bool R1L = false, bool PFX = false, bool PW1 = false, bool W16 = false>
+// ST: the tail also writes the decode status (qpd_decode_status: the output path's
+// metric and CRC verdict, the CRC mask) -- instantiations of their own (the *_st.hip
+// units), so that the plain decode kernels compile to what they are without it.
+template <int KIND, int NS, bool L8, bool R1L = false, bool PFX = false, bool PW1 = false, bool W16 = false,
+          bool ST = false>
 __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
                                 : W16 ? QPD_WPE_W16
                                 : NS == 2 ? (KIND == K_SCL_LUT && !PFX ? QPD_WPE2_SCL : KIND == K_FASTSCL_LUT ? QPD_WPE2_FSCL : QPD_WPE2)
                                 : KIND == K_FASTSCL_LUT ? QPD_WPE_FSCL : QPD_WPE1) void lut_fast_kernel(FastPlan P, const int32_t *__restrict__ in, int64_t B,
                                                                uint8_t *__restrict__ out,
-                                                               const MOp *__restrict__ ops) {
+                                                               const MOp *__restrict__ ops, FastStatus SO) {
     constexpr bool kList = (KIND == K_SCL_LUT || KIND == K_FASTSCL_LUT);
     static_assert(!W16 || (!L8 && (KIND == K_SCL_LUT || (KIND == K_FASTSCL_LUT && !R1L && !PFX))),
                   "W16: SCL-LUT / FastSCL-LUT list sizes 9..16");
+    static_assert(!ST || (kList && !PFX), "ST: the list kinds' decode kernels");
     constexpr int LM = L8 ? 8 : W16 ? 16 : 0;  // list mode of the leaf forks (leaf_fork)
     // staged BOT3 loads: the list kinds (SCL-LUT, FastSCL-LUT)
     constexpr bool kLazy = QPD_BOT3_LAZY && kList;
@@ -474,9 +489,10 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
         for (int s = 0; s < NS; ++s) {
             const Mem &M = Mv[s];
             int best = 0;
+            bool passed = false;
             if (kList && P.crc_n > 0) {
                 best = ca_winner(stv[s].pm, gl, gbase, L, N, P.info_mask, P.ca_A, P.K - P.ca_A, P.crc_n, P.crc_q,
-                                 [&](int w) { return M.ld(rl, r0 + w, lane); });
+                                 [&](int w) { return M.ld(rl, r0 + w, lane); }, ST ? SO.crc_mask : 0u, &passed);
             } else if (kList) {
                 double bpm = shfld(stv[s].pm, gbase);
                 for (int j = 1; j < L; ++j) {
@@ -511,6 +527,13 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
                 wave_sync();
             }
             const int64_t frame = (task * NS + s) * fpw + lane / gs;
+            if constexpr (ST) {  // the output path's own metric and verdict, by the group's first lane
+                const double wpm = shfld(stv[s].pm, src);
+                if (gl == 0 && frame < B) {
+                    if (SO.st_metric) SO.st_metric[frame] = wpm;
+                    if (SO.st_pass) SO.st_pass[frame] = (uint8_t)passed;
+                }
+            }
             if (frame < B) {
                 auto bit = [&](int pos) {
                     const int w = pos >> 5;

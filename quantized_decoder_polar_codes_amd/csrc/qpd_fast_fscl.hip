@@ -11,8 +11,8 @@
 
 namespace qpd {
 
-const void *fast_kernel_fscl(int sets, bool l8, bool r1l) {
-#define QPD_F(S, E, R) reinterpret_cast<const void *>(&lut_fast_kernel<K_FASTSCL_LUT, S, E, R>)
+const void *QPD_UNIT_FN(fast_kernel_fscl)(int sets, bool l8, bool r1l) {
+#define QPD_F(S, E, R) reinterpret_cast<const void *>(&lut_fast_kernel<K_FASTSCL_LUT, S, E, R, false, false, false, QPD_ST>)
     if (r1l) {
         if (sets == 2) return l8 ? QPD_F(2, true, true) : QPD_F(2, false, true);
         return l8 ? QPD_F(1, true, true) : QPD_F(1, false, true);

@@ -8,9 +8,9 @@
 
 namespace qpd {
 
-const void *fast_kernel_fscl_pw1(int sets, bool l8, bool r1l) {
+const void *QPD_UNIT_FN(fast_kernel_fscl_pw1)(int sets, bool l8, bool r1l) {
     if (sets != 2 || !l8 || r1l) return nullptr;
-    return reinterpret_cast<const void *>(&lut_fast_kernel<K_FASTSCL_LUT, 2, true, false, false, true>);
+    return reinterpret_cast<const void *>(&lut_fast_kernel<K_FASTSCL_LUT, 2, true, false, false, true, false, QPD_ST>);
 }
 
 }  // namespace qpd

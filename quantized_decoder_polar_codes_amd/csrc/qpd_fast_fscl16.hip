@@ -11,8 +11,8 @@
 
 namespace qpd {
 
-const void *fast_kernel_fscl_w16(int sets, bool pw1) {
-#define QPD_FW(S, P) reinterpret_cast<const void *>(&lut_fast_kernel<K_FASTSCL_LUT, S, false, false, false, P, true>)
+const void *QPD_UNIT_FN(fast_kernel_fscl_w16)(int sets, bool pw1) {
+#define QPD_FW(S, P) reinterpret_cast<const void *>(&lut_fast_kernel<K_FASTSCL_LUT, S, false, false, false, P, true, QPD_ST>)
     if (sets == 2) return pw1 ? QPD_FW(2, true) : QPD_FW(2, false);
     if (sets == 1) return pw1 ? QPD_FW(1, true) : QPD_FW(1, false);
     return nullptr;

@@ -1,0 +1,5 @@
+// qpd_fast_fscl_st.hip -- the decode-status instantiations (lut_fast_kernel<..., ST = true>,
+// qpd_fast.hip: qpd_decode_status) of qpd_fast_fscl.hip's kernels (FastSCL-LUT, two pointer words per path),
+// as a unit of their own: the plain instantiations compile to what they were.
+#define QPD_STATUS_UNIT 1
+#include "qpd_fast_fscl.hip"

@@ -49,6 +49,16 @@ struct FastPlan {
 #endif
 };
 
+// Decode status (qpd_decode_status), per launch: the decode kernels' last argument,
+// read by the ST instantiations' tail alone.  Not part of FastPlan: the plan is the
+// first kernel argument, and growing it moves the others -- this way the plain
+// instantiations compile to the instructions they had before the status existed.
+struct FastStatus {
+    uint32_t crc_mask;   // XORed onto the CRC register's low bits before the compare (ca_winner)
+    double *st_metric;   // [B] path metric of the output path, or NULL
+    uint8_t *st_pass;    // [B] 1 = the output path passed the CRC, or NULL
+};
+
 // Row access in either space.  `in_lds` is wave-uniform.  The global slab is
 // reached through a buffer descriptor (32-bit lane offsets; distinct
 // instructions, so the compiler never folds the two spaces into one flat

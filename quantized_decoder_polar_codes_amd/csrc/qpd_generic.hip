@@ -75,6 +75,10 @@ struct DevPlan {
     int32_t *err;
     uint32_t *task_ctr;  // task queue: groups taken (never reset; see wave_take)
     uint32_t task_base;  // per launch: the counter's value when this launch's takes begin
+    // Decode status (qpd_decode_status), per launch; NULL / 0 in every other call.
+    uint32_t crc_mask;   // XORed onto the CRC register's low bits before the compare (ca_winner)
+    double *st_metric;   // [B] path metric of the output path, or NULL
+    uint8_t *st_pass;    // [B] 1 = the output path passed the CRC, or NULL
 };
 
 __device__ __forceinline__ double vcl_at(const DevPlan &P, int row, int pos, int sym) {
@@ -698,10 +702,12 @@ __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
         wave_sync();
         // best path: first minimum of the path metrics (H6, SCLLUTDecoder.cpp:244)
         int best = 0;
+        bool passed = false;
         if (kList && P.crc_n > 0) {
             check_keys<DOM>(P, pm, pm);  // the CA epilogue sorts the metrics
             best = ca_winner_ranked(grank<ML>(pm, gl, gbase, L, sh), gl, gbase, L, P.N, P.info_mask, P.ca_A, P.ca_chk,
-                                    P.crc_n, P.crc_q, [&](int w) { return row_ptr(wsc, P.Ro + w)[lane]; });
+                                    P.crc_n, P.crc_q, [&](int w) { return row_ptr(wsc, P.Ro + w)[lane]; }, P.crc_mask,
+                                    &passed);
         } else if (kList) {
             double bpm = shfld(pm, gbase);
             for (int j = 1; j < L; ++j) {
@@ -709,6 +715,15 @@ __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
                 if (pj < bpm) {
                     bpm = pj;
                     best = j;
+                }
+            }
+        }
+        if constexpr (kList) {
+            if (P.st_metric || P.st_pass) {  // wave-uniform: the output path's own metric and verdict
+                const double wpm = shfld(pm, gbase + best);
+                if (gl == 0 && frame_ok) {
+                    if (P.st_metric) P.st_metric[frame] = wpm;
+                    if (P.st_pass) P.st_pass[frame] = (uint8_t)passed;
                 }
             }
         }

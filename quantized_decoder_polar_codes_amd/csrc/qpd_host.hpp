@@ -200,6 +200,14 @@ class Engine {
         r1_ord.assign((size_t)L * (max_r1 + 1), 0);
     }
 
+    // Decode status (qpd_decode_status_host): crc_mask is XORed onto the CRC
+    // register's low bits before the compare (CASCLWithRNTI.cpp:222-224; 0: none);
+    // after a decode, the output path's own metric (list kinds) and whether it
+    // passed the CRC compare (CRC-aided kinds).
+    uint32_t crc_mask = 0;
+    double last_metric = 0.0;
+    bool last_pass = false;
+
     // One frame: y[N] (int32 symbols or float64 LLRs) -> out[out_k].
     // Returns 0, or qpd::ERR_SYMBOL for a channel symbol outside [0, v).
     template <class In>
@@ -618,6 +626,7 @@ class Engine {
     void finish(uint8_t *out) {
         const int L = P.L;
         int best = 0;
+        last_pass = false;
         if (L > 1 && P.crc_n > 0) {
             // CA epilogue (CASCLLUTDecoder.cpp:263-290): paths in argsort(PML)
             // order, the first whose A info bits reproduce the check bits under
@@ -636,11 +645,12 @@ class Engine {
                         const uint32_t fb = bit ^ ((reg & top) ? 1u : 0u);
                         reg = ((reg << 1) & mask) ^ (P.crc_q & (0u - fb));
                     } else {
-                        pass = pass && bit == ((reg >> (P.crc_n - 1 - (t - P.ca_A))) & 1u);
+                        pass = pass && bit == (((reg ^ crc_mask) >> (P.crc_n - 1 - (t - P.ca_A))) & 1u);
                     }
                 }
                 if (pass) {
                     best = idx[r];
+                    last_pass = true;
                     break;
                 }
             }
@@ -648,6 +658,7 @@ class Engine {
             for (int j = 1; j < L; ++j)
                 if (pm[j] < pm[best]) best = j;  // first minimum (H6, SCLLUTDecoder.cpp:244)
         }
+        last_metric = pm[best];
         const uint64_t *x = reencode(best);
         for (int t = 0; t < P.out_k; ++t) out[t] = bit(x, P.info_pos[t]);
     }

@@ -6,9 +6,9 @@
 
 namespace qpd {
 
-const void *fast_kernel_scl(int sets, bool l8, bool w16) {
-#define QPD_FK(S, E) reinterpret_cast<const void *>(&lut_fast_kernel<K_SCL_LUT, S, E>)
-#define QPD_FW(S) reinterpret_cast<const void *>(&lut_fast_kernel<K_SCL_LUT, S, false, false, false, false, true>)
+const void *QPD_UNIT_FN(fast_kernel_scl)(int sets, bool l8, bool w16) {
+#define QPD_FK(S, E) reinterpret_cast<const void *>(&lut_fast_kernel<K_SCL_LUT, S, E, false, false, false, false, QPD_ST>)
+#define QPD_FW(S) reinterpret_cast<const void *>(&lut_fast_kernel<K_SCL_LUT, S, false, false, false, false, true, QPD_ST>)
     if (w16) return sets == 2 ? QPD_FW(2) : sets == 1 ? QPD_FW(1) : nullptr;
 #ifdef QPD_SETS3
     if (sets == 3 && l8) return QPD_FK(3, true);

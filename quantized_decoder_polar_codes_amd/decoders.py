@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import ctypes
 import threading
+from typing import NamedTuple
 
 import numpy as np
 
@@ -31,7 +32,7 @@ from . import _lib
 from .lut import PackedLUT, pack_luts
 from .quant import LloydQuant, UniformQuant, pack_lloyd, pack_uniform
 
-__all__ = ["ChannelQuantizer", "SCDecoder", "SCLUTDecoder", "SCLLUTDecoder", "FastSCLUTDecoder", "FastSCLLUTDecoder",
+__all__ = ["ChannelQuantizer", "DecodeStatus", "SCDecoder", "SCLUTDecoder", "SCLLUTDecoder", "FastSCLUTDecoder", "FastSCLLUTDecoder",
            "CASCLLUTDecoder", "CAFastSCLLUTDecoder", "SCLDecoder", "CASCLDecoder", "FastSCDecoder", "FastSCLDecoder",
            "SCUniformQuantizedDecoder", "SCLUniformQuantizedDecoder", "SCLloydQuantizedDecoder",
            "SCLLloydQuantizedDecoder"]
@@ -48,6 +49,16 @@ def _as_i32(x) -> np.ndarray:
 
 def _ptr(a):
     return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
+class DecodeStatus(NamedTuple):
+    """What ``decode_batch(..., return_status=True)`` returns beside the bits, per frame:
+    ``metric`` (float64 [B]), the path metric of the output path, and ``crc_pass`` (bool [B];
+    None for a decoder without CRC), whether that path passed the CRC compare
+    (qpd_decode_status, include/qpd.h).  numpy arrays or torch CUDA tensors, as the bits."""
+
+    metric: object
+    crc_pass: object
 
 
 def _torch():
@@ -220,12 +231,63 @@ class _DecoderBase:
         return {name: (ms[i], n[i]) for i, name in enumerate(("pre", "decode", "mc", "pfx"))}
 
     # -- decoding --------------------------------------------------------------
-    def decode_batch(self, x):
+    @property
+    def _crc_aided(self) -> bool:
+        return self._kind in (_lib.QPD_CASCL_LUT, _lib.QPD_CAFASTSCL_LUT, _lib.QPD_CASCL_FLOAT)
+
+    def _decode_status(self, x, crc_mask):
+        """decode_batch(x, return_status=True, crc_mask): qpd_decode_status / _host."""
+        torch = _torch()
+        lib = _lib.load()
+        mask = None
+        sa = _lib.QpdStatusArgs()
+        if crc_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(crc_mask).reshape(-1).astype(np.uint8))
+            sa.crc_mask, sa.crc_mask_bits = _ptr(mask), mask.size
+        if torch is not None and isinstance(x, torch.Tensor) and x.is_cuda:
+            u8 = not self._float_input and x.dtype == torch.uint8
+            want = torch.float64 if self._float_input else torch.uint8 if u8 else torch.int32
+            xs = x.reshape(-1, self.N).to(want).contiguous()
+            B = xs.shape[0]
+            out = torch.empty((B, self.out_bits), dtype=torch.uint8, device=xs.device)
+            metric = torch.empty(B, dtype=torch.float64, device=xs.device)
+            flag = torch.empty(B, dtype=torch.uint8, device=xs.device) if self._crc_aided else None
+            sa.metric = ctypes.c_void_p(metric.data_ptr())
+            sa.crc_pass = None if flag is None else ctypes.c_void_p(flag.data_ptr())
+            ty = _lib.QPD_IN_F64 if self._float_input else _lib.QPD_IN_U8 if u8 else _lib.QPD_IN_I32
+            stream = torch.cuda.current_stream(xs.device).cuda_stream
+            _lib.check(lib.qpd_decode_status(self._h, ctypes.c_void_p(xs.data_ptr()), ty, B,
+                                             ctypes.c_void_p(out.data_ptr()), ctypes.byref(sa), ctypes.c_void_p(stream)))
+            return out, DecodeStatus(metric, None if flag is None else flag.bool())
+        if torch is not None and isinstance(x, torch.Tensor):
+            x = x.numpy()
+        a = np.asarray(x)
+        u8 = not self._float_input and a.dtype == np.uint8
+        want = np.float64 if self._float_input else np.uint8 if u8 else np.int32
+        a = np.ascontiguousarray(a.astype(want, copy=False).reshape(-1, self.N))
+        B = a.shape[0]
+        out = np.empty((B, self.out_bits), dtype=np.uint8)
+        metric = np.zeros(B, dtype=np.float64)
+        flag = np.zeros(B, dtype=np.uint8) if self._crc_aided else None
+        sa.metric, sa.crc_pass = _ptr(metric), _ptr(flag)
+        ty = _lib.QPD_IN_F64 if self._float_input else _lib.QPD_IN_U8 if u8 else _lib.QPD_IN_I32
+        _lib.check(lib.qpd_decode_status_host(self._h, _ptr(a), ty, B, _ptr(out), ctypes.byref(sa)))
+        return out, DecodeStatus(metric, None if flag is None else flag.astype(bool))
+
+    def decode_batch(self, x, return_status: bool = False, crc_mask=None):
         """Decode B frames.  numpy [B, N] -> numpy uint8 [B, K] (synchronous);
         torch CUDA tensor [B, N] -> torch CUDA uint8 [B, K] on the current stream.
         (A instead of K for the CRC-aided decoders.)  LUT decoders: uint8 symbols
         go to the library as they are (qpd_decode_u8 / qpd_decode_u8_host, a
-        quarter of the bytes); any other dtype is converted to int32."""
+        quarter of the bytes); any other dtype is converted to int32.
+        ``return_status=True`` (list decoders): ``(bits, DecodeStatus)`` -- the output
+        path's metric and, for the CRC-aided decoders, whether it passed the CRC;
+        ``crc_mask`` (0/1 entries, at most crc_n; with return_status): XORed onto the tail
+        of the computed CRC before the compare, e.g. the RNTI of a blind detection."""
+        if return_status:
+            return self._decode_status(x, crc_mask)
+        if crc_mask is not None:
+            raise ValueError("crc_mask needs return_status=True")
         torch = _torch()
         lib = _lib.load()
         if torch is not None and isinstance(x, torch.Tensor) and x.is_cuda:
