@@ -48,6 +48,12 @@ def lib():
         L.orc_decode_float.argtypes = [i32, i32, i32, i32, P, P, i32, P, P, P, P, P, P, P, P, i32, i32, P, i32, P,
                                        i64, P]
         L.orc_decode_float.restype = ctypes.c_int
+        L.orc_decode_lut_status.argtypes = [i32, i32, i32, i32, i32, i32, P, P, P, P, i32, P, P, i32, P, i32, i32, P,
+                                            i32, P, i32, P, i64, P, P, P, P]
+        L.orc_decode_lut_status.restype = ctypes.c_int
+        L.orc_decode_float_status.argtypes = [i32, i32, i32, i32, P, P, i32, P, P, P, P, P, P, P, P, i32, i32, P, i32,
+                                              P, i32, P, i64, P, P, P, P]
+        L.orc_decode_float_status.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -102,6 +108,39 @@ def decode_lut_ca(kind: str, packed, K: int, A: int, L: int, frozen, symbols, no
     return out
 
 
+def _status_out(B, L, mask):
+    mask = np.zeros(0, dtype=np.uint8) if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    return mask, np.zeros((B, L)), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.uint8)
+
+
+def decode_lut_status(kind: str, packed, K: int, L: int, frozen, symbols, node_type=None, A: int = 0, crc_n: int = 24,
+                      crc_loc=CRC24_LOC, mask=None):
+    """A LUT list kind ("SCL-LUT", "FastSCL-LUT"; with A, "CA-SCL-LUT", "CA-FastSCL-LUT") with what its
+    last step knows: (bits [B, K or A], pml [B, L] every path's final metric in path-index order,
+    winner [B] the output path's index, passed [B] bool, its CRC compare succeeded).  ``mask``: 0/1
+    entries, entry l XORed onto check-code bit crc_n - len(mask) + l before the compare."""
+    base = {"SCL-LUT": 2, "FastSCL-LUT": 4, "CA-SCL-LUT": 2, "CA-FastSCL-LUT": 4}[kind]
+    if kind.startswith("CA-") != (A > 0):
+        raise ValueError("A goes with the CRC-aided kinds")
+    N = packed.N
+    sym = np.ascontiguousarray(np.asarray(symbols, dtype=np.int32).reshape(-1, N))
+    B = sym.shape[0]
+    out = np.zeros((B, A or K), dtype=np.uint8)
+    frozen = np.ascontiguousarray(np.asarray(frozen, dtype=np.int32))
+    nt = None if node_type is None else np.ascontiguousarray(np.asarray(node_type).astype(np.int32))
+    loc = np.ascontiguousarray(np.asarray(crc_loc, dtype=np.int32))
+    mask, pml, winner, passed = _status_out(B, L, mask)
+    rc = lib().orc_decode_lut_status(base, N, K, A, L, packed.v, _ptr(frozen), _ptr(nt),
+                                     _ptr(packed.lut_f), _ptr(packed.f_base), packed.f_step,
+                                     _ptr(packed.lut_g), _ptr(packed.g_base), packed.g_step,
+                                     _ptr(packed.vcl), packed.vcl_rows, crc_n if A else 0, _ptr(loc), len(loc) if A else 0,
+                                     _ptr(mask), len(mask), _ptr(sym), B, _ptr(out), _ptr(pml), _ptr(winner),
+                                     _ptr(passed))
+    if rc != 0:
+        raise RuntimeError(f"oracle decode failed rc={rc}")
+    return out, pml, winner.astype(np.int64), passed.astype(bool)
+
+
 def crc_encode(info, crc_n: int = 24, crc_loc=CRC24_LOC) -> np.ndarray:
     """CRC::encoding (utils.cpp:77-92) on rows of `info` (uint8 [B, A]) -> check bits [B, crc_n]."""
     info = np.atleast_2d(np.asarray(info, dtype=np.uint8))
@@ -135,6 +174,17 @@ def decode_float(kind: str, N: int, K: int, frozen, llr, L: int = 1, node_type=N
                  crc_n: int = 0, crc_loc=()) -> np.ndarray:
     """Restated float-domain decoder ``kind`` on float64 LLRs [B, N] -> uint8 [B, K] ([B, A] for CA-SCL).
     ``quant``: quant.UniformQuant (Uniform kinds) or quant.LloydQuant (Lloyd kinds)."""
+    return _decode_float(kind, N, K, frozen, llr, L, node_type, quant, A, crc_n, crc_loc, None, False)
+
+
+def decode_float_status(kind: str, N: int, K: int, frozen, llr, L: int = 1, node_type=None, quant=None, A: int = 0,
+                        crc_n: int = 0, crc_loc=(), mask=None):
+    """A float list kind with (bits, pml [B, L], winner [B], passed [B]) as decode_lut_status; ``mask``
+    for CA-SCL only."""
+    return _decode_float(kind, N, K, frozen, llr, L, node_type, quant, A, crc_n, crc_loc, mask, True)
+
+
+def _decode_float(kind, N, K, frozen, llr, L, node_type, quant, A, crc_n, crc_loc, mask, status):
     k = FLOAT_KIND[kind]
     x = np.ascontiguousarray(np.asarray(llr, dtype=np.float64).reshape(-1, N))
     B = x.shape[0]
@@ -152,12 +202,17 @@ def decode_float(kind: str, N: int, K: int, frozen, llr, L: int = 1, node_type=N
         else:
             bnd, boff, blen, rec, roff, rlen = (quant.bnd, quant.bnd_off, quant.bnd_len, quant.rec, quant.rec_off,
                                                 quant.rec_len)
-    rc = lib().orc_decode_float(k, N, K, L, _ptr(frozen), _ptr(nt), v, _ptr(rf), _ptr(rg), _ptr(bnd), _ptr(boff),
-                                _ptr(blen), _ptr(rec), _ptr(roff), _ptr(rlen), A, crc_n, _ptr(loc), loc.size,
-                                _ptr(x), B, _ptr(out))
+    code = (k, N, K, L, _ptr(frozen), _ptr(nt), v, _ptr(rf), _ptr(rg), _ptr(bnd), _ptr(boff), _ptr(blen), _ptr(rec),
+            _ptr(roff), _ptr(rlen), A, crc_n, _ptr(loc), loc.size)
+    if not status:
+        rc = lib().orc_decode_float(*code, _ptr(x), B, _ptr(out))
+    else:
+        mask, pml, winner, passed = _status_out(B, L, mask)
+        rc = lib().orc_decode_float_status(*code, _ptr(mask), len(mask), _ptr(x), B, _ptr(out), _ptr(pml), _ptr(winner),
+                                           _ptr(passed))
     if rc != 0:
         raise RuntimeError(f"oracle decode failed rc={rc}")
-    return out
+    return (out, pml, winner.astype(np.int64), passed.astype(bool)) if status else out
 
 
 def reference_module():

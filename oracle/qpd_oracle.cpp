@@ -136,6 +136,14 @@ struct CaSpec {
     int nchk = 0;  // bits compared after the A info bits: K - A (LUT kinds,
                    // CASCLLUTDecoder.cpp:279) or crc_n (CASCLDecoder.cpp:223)
     std::vector<int> p;  // crc_n + 1 coefficients
+    std::vector<uint8_t> mask;  // 0 / 1, XORed onto check-code bits [crc_n - size, crc_n) (CASCLWithRNTI.cpp:222-224)
+};
+
+// What a list decode knows at its end beside the output bits.
+struct Status {
+    std::vector<double> pml;  // every path's final metric, in path-index order
+    int winner = 0;           // index of the output path
+    bool passed = false;      // CRC-aided: the output path's compare succeeded
 };
 
 int first_argmin(const std::vector<double> &x) {
@@ -532,7 +540,7 @@ struct SCLDec {
     }
 
     template <class In>
-    int run(const In *y, uint8_t *out) {
+    int run(const In *y, uint8_t *out, Status *st = nullptr) {
         const int N = c.N, n = c.n;
         if (fast && c.type(0) >= 0 && c.type(0) <= 2) return -2;  // reference UB (root special)
         path.assign(L, Path{std::vector<Block<T>>(n + 1), std::vector<Block<uint8_t>>(2 * (n + 1))});
@@ -546,44 +554,52 @@ struct SCLDec {
         if (dom.bad()) return -4;
         for (double p : pm)
             if (std::isnan(p)) return -4;  // NaN keys: std::sort's order is undefined
+        std::vector<uint8_t> info = epilogue(st);
+        std::memcpy(out, info.data(), info.size());
+        return 0;
+    }
+
+    // Decoded info bits of a path: the leaf decisions (SCL, :244-252 / :268-275) or the re-encoded root
+    // partial sums (FastSCL, :338-355 / :387-406) -- the same bits, the combines being the polar
+    // transform and the transform its own inverse.
+    std::vector<uint8_t> info_of(int pth) const {
+        std::vector<uint8_t> x(U(pth, 0, 0), U(pth, 0, 0) + c.N);
+        reencode(x, c.N);
+        std::vector<uint8_t> info(c.K);
+        emit_info(c, x.data(), info.data());
+        return info;
+    }
+
+    // The one output stage of every list kind: the output path, its bits, and (st) what the reference
+    // computes beside them and drops.  No CRC: the first minimum of PML (H6).  CRC-aided
+    // (CASCLLUTDecoder.cpp:263-302, CASCLDecoder.cpp:202-235): the first path in argsort(PML) order
+    // whose check code, the mask XORed onto its tail (CASCLWithRNTI.cpp:222-224), equals the nchk
+    // bits after the A info bits; else the first in that order.
+    std::vector<uint8_t> epilogue(Status *st) const {
+        int winner = first_argmin(pm);
+        bool passed = false;
+        std::vector<uint8_t> info;
         if (ca.A > 0) {
-            // decoded info bits of a path: the leaf decisions (SCL, :268-275) or the re-encoded root
-            // partial sums (FastSCL, :338-355) -- the same bits, the combines being the polar transform
-            // and the transform its own inverse
-            auto info_of = [&](int pth) {
-                std::vector<uint8_t> x(U(pth, 0, 0), U(pth, 0, 0) + N);
-                reencode(x, N);
-                std::vector<uint8_t> info;
-                for (int k = 0; k < N; ++k)
-                    if (c.frozen[k] == 0) info.push_back(x[k]);
-                return info;
-            };
             std::vector<int> order = sort_index(pm);
-            int winner = order[0];
-            for (int i = 0; i < L; ++i) {
-                std::vector<uint8_t> info = info_of(order[i]);
+            winner = order[0];
+            for (int i = 0; i < L && !passed; ++i) {
+                info = info_of(order[i]);
                 std::vector<uint8_t> head(info.begin(), info.begin() + ca.A);
                 std::vector<uint8_t> chk = crc_encoding(head, ca.crc_n, ca.p);
-                bool pass = true;
-                for (int j = 0; j < ca.nchk; ++j)
-                    if (chk[j] != info[ca.A + j]) {
-                        pass = false;
-                        break;
-                    }
-                if (pass) {
-                    winner = order[i];
-                    break;
-                }
+                const int m = (int)ca.mask.size();
+                for (int l = 0; l < m; ++l) chk[ca.crc_n - m + l] ^= ca.mask[l];
+                passed = std::equal(chk.begin(), chk.begin() + ca.nchk, info.begin() + ca.A);
+                if (passed) winner = order[i];
             }
-            std::vector<uint8_t> info = info_of(winner);
-            std::memcpy(out, info.data(), ca.A);
-            return 0;
         }
-        int best = first_argmin(pm);  // H6
-        std::vector<uint8_t> x(U(best, 0, 0), U(best, 0, 0) + N);  // :244-252 (the leaf decisions) / :387-406
-        reencode(x, N);
-        emit_info(c, x.data(), out);
-        return 0;
+        if (!passed) info = info_of(winner);
+        if (ca.A > 0) info.resize(ca.A);
+        if (st) {
+            st->pml = pm;
+            st->winner = winner;
+            st->passed = passed;
+        }
+        return info;
     }
 };
 
@@ -609,9 +625,61 @@ Code make_code(int32_t N, int32_t K, int32_t L, int32_t v, const int32_t *frozen
     return c;
 }
 
+// CRC of a CRC-aided decode; false for a mask that is longer than the check code or not of 0 / 1.
+bool set_crc(CaSpec &ca, int A, int crc_n, int nchk, const int32_t *crc_loc, int n_loc, const uint8_t *mask,
+             int mask_bits) {
+    if (mask_bits < 0 || mask_bits > crc_n) return false;
+    ca.A = A;
+    ca.crc_n = crc_n;
+    ca.nchk = nchk;
+    ca.p.assign(crc_n + 1, 0);
+    for (int i = 0; i < n_loc; ++i) ca.p[crc_loc[i]] = 1;
+    ca.mask.assign(mask, mask + mask_bits);
+    for (uint8_t m : ca.mask)
+        if (m > 1) return false;
+    return true;
+}
+
+// Frames [0, B) through a list decoder; pml [B][L], winner [B], passed [B] where asked for.
+template <class D, class In>
+int decode_list(SCLDec<D> &dec, const In *in, int N, int64_t B, uint8_t *out, int ob, double *pml, int32_t *winner,
+                uint8_t *passed) {
+    Status st;
+    for (int64_t b = 0; b < B; ++b) {
+        int rc = dec.run(in + b * N, out + b * ob, &st);
+        if (rc) return rc;
+        if (pml) std::copy(st.pml.begin(), st.pml.end(), pml + b * dec.L);
+        if (winner) winner[b] = st.winner;
+        if (passed) passed[b] = st.passed;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+// List kinds with status: kind 2 = SCL-LUT / CA-SCL-LUT, 4 = FastSCL-LUT / CA-FastSCL-LUT; A == 0: no CRC
+// (out uint8 [B][K]), else the CRC-aided decoder (out [B][A]; crc_loc lists the nonzero coefficient
+// indices, CRC::CRC, utils.cpp:69-75).  mask: mask_bits entries of 0 / 1, entry l XORed onto check-code
+// bit crc_n - mask_bits + l before the compare (CASCLWithRNTI.cpp:222-224).  pml [B][L]: every path's final
+// metric in path-index order; winner [B]: the output path's index; passed [B]: its CRC compare
+// succeeded (0 without CRC).  Each of the three may be null.
+int orc_decode_lut_status(int32_t kind, int32_t N, int32_t K, int32_t A, int32_t L, int32_t v, const int32_t *frozen,
+                          const int32_t *node_type, const uint8_t *lut_f, const int32_t *f_base, int32_t f_step,
+                          const uint8_t *lut_g, const int32_t *g_base, int32_t g_step, const double *vcl,
+                          int32_t vcl_rows, int32_t crc_n, const int32_t *crc_loc, int32_t n_loc, const uint8_t *mask,
+                          int32_t mask_bits, const int32_t *sym, int64_t B, uint8_t *out, double *pml,
+                          int32_t *winner, uint8_t *passed) {
+    if (kind != 2 && kind != 4) return -3;
+    if (A < 0 || A > K || (A > 0 && K - A > crc_n) || (A == 0 && mask_bits != 0)) return -1;
+    Code c = make_code(N, K, L, v, frozen, node_type, lut_f, f_base, f_step, lut_g, g_base, g_step, vcl, vcl_rows);
+    if (N < 2 || (1 << c.n) != N) return -1;
+    LutDom dom{c};
+    SCLDec<LutDom> dec(c, dom, kind == 4);
+    if (A > 0 && !set_crc(dec.ca, A, crc_n, K - A, crc_loc, n_loc, mask, mask_bits)) return -1;
+    return decode_list(dec, sym, N, B, out, A > 0 ? A : K, pml, winner, passed);
+}
 
 // kind: 1 = SC-LUT, 2 = SCL-LUT, 3 = FastSC-LUT, 4 = FastSCL-LUT.
 // Decodes frames [0, B) of `sym` (int32 [B][N]) into `out` (uint8 [B][K]).
@@ -619,53 +687,34 @@ int orc_decode_lut(int32_t kind, int32_t N, int32_t K, int32_t L, int32_t v, con
                    const int32_t *node_type, const uint8_t *lut_f, const int32_t *f_base, int32_t f_step,
                    const uint8_t *lut_g, const int32_t *g_base, int32_t g_step, const double *vcl,
                    int32_t vcl_rows, const int32_t *sym, int64_t B, uint8_t *out) {
-    Code c = make_code(N, K, kind == 2 || kind == 4 ? L : 1, v, frozen, node_type, lut_f, f_base, f_step, lut_g,
-                       g_base, g_step, vcl, vcl_rows);
+    if (kind == 2 || kind == 4)
+        return orc_decode_lut_status(kind, N, K, 0, L, v, frozen, node_type, lut_f, f_base, f_step, lut_g, g_base,
+                                     g_step, vcl, vcl_rows, 0, nullptr, 0, nullptr, 0, sym, B, out, nullptr, nullptr,
+                                     nullptr);
+    if (kind != 1 && kind != 3) return -3;
+    Code c = make_code(N, K, 1, v, frozen, node_type, lut_f, f_base, f_step, lut_g, g_base, g_step, vcl, vcl_rows);
     if (N < 2 || (1 << c.n) != N) return -1;
     LutDom dom{c};
-    if (kind == 1 || kind == 3) {
-        SCDec<LutDom> dec(c, dom, kind == 3);
-        for (int64_t b = 0; b < B; ++b) {
-            int rc = dec.run(sym + b * N, out + b * K);
-            if (rc) return rc;
-        }
-        return 0;
+    SCDec<LutDom> dec(c, dom, kind == 3);
+    for (int64_t b = 0; b < B; ++b) {
+        int rc = dec.run(sym + b * N, out + b * K);
+        if (rc) return rc;
     }
-    if (kind == 2 || kind == 4) {
-        SCLDec<LutDom> dec(c, dom, kind == 4);
-        for (int64_t b = 0; b < B; ++b) {
-            int rc = dec.run(sym + b * N, out + b * K);
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    return -3;
+    return 0;
 }
 
 // CRC-aided list decoders: kind 2 = CA-SCL-LUT, 4 = CA-FastSCL-LUT (the
-// list kinds above plus the CRC epilogue).  crc_loc lists the nonzero
-// coefficient indices (CRC::CRC, utils.cpp:69-75).  Output uint8 [B][A].
+// list kinds above plus the CRC epilogue).  Output uint8 [B][A].
 int orc_decode_lut_ca(int32_t kind, int32_t N, int32_t K, int32_t A, int32_t L, int32_t v, const int32_t *frozen,
                       const int32_t *node_type, const uint8_t *lut_f, const int32_t *f_base, int32_t f_step,
                       const uint8_t *lut_g, const int32_t *g_base, int32_t g_step, const double *vcl,
                       int32_t vcl_rows, int32_t crc_n, const int32_t *crc_loc, int32_t n_loc, const int32_t *sym,
                       int64_t B, uint8_t *out) {
     if (kind != 2 && kind != 4) return -3;
-    if (A < 1 || A > K || K - A > crc_n) return -1;
-    Code c = make_code(N, K, L, v, frozen, node_type, lut_f, f_base, f_step, lut_g, g_base, g_step, vcl, vcl_rows);
-    if (N < 2 || (1 << c.n) != N) return -1;
-    LutDom dom{c};
-    SCLDec<LutDom> dec(c, dom, kind == 4);
-    dec.ca.A = A;
-    dec.ca.crc_n = crc_n;
-    dec.ca.nchk = K - A;
-    dec.ca.p.assign(crc_n + 1, 0);
-    for (int i = 0; i < n_loc; ++i) dec.ca.p[crc_loc[i]] = 1;
-    for (int64_t b = 0; b < B; ++b) {
-        int rc = dec.run(sym + b * N, out + b * A);
-        if (rc) return rc;
-    }
-    return 0;
+    if (A < 1) return -1;
+    return orc_decode_lut_status(kind, N, K, A, L, v, frozen, node_type, lut_f, f_base, f_step, lut_g, g_base, g_step,
+                                 vcl, vcl_rows, crc_n, crc_loc, n_loc, nullptr, 0, sym, B, out, nullptr, nullptr,
+                                 nullptr);
 }
 
 // Float SC (min-sum), SCDecoder.cpp:14-89.  llr is float64 [B][N].
@@ -692,11 +741,14 @@ int orc_decode_sc_float(int32_t N, int32_t K, const int32_t *frozen, const doubl
 // Output uint8 [B][K] ([B][A] for kind 8).  Returns -4 where the reference's
 // behaviour is undefined (Lloyd index outside the reconstruction, NaN path
 // metrics).
-int orc_decode_float(int32_t kind, int32_t N, int32_t K, int32_t L, const int32_t *frozen, const int32_t *node_type,
-                     int32_t v, const double *r_f, const double *r_g, const double *bnd, const int32_t *bnd_off,
-                     const int32_t *bnd_len, const double *rec, const int32_t *rec_off, const int32_t *rec_len,
-                     int32_t A, int32_t crc_n, const int32_t *crc_loc, int32_t n_loc, const double *llr, int64_t B,
-                     uint8_t *out) {
+// With status (list kinds; mask, pml, winner, passed as orc_decode_lut_status, the mask for kind 8 only):
+// each of pml, winner, passed may be null, and all are for the SC kinds.
+int orc_decode_float_status(int32_t kind, int32_t N, int32_t K, int32_t L, const int32_t *frozen,
+                            const int32_t *node_type, int32_t v, const double *r_f, const double *r_g, const double *bnd,
+                            const int32_t *bnd_off, const int32_t *bnd_len, const double *rec, const int32_t *rec_off,
+                            const int32_t *rec_len, int32_t A, int32_t crc_n, const int32_t *crc_loc, int32_t n_loc,
+                            const uint8_t *mask, int32_t mask_bits, const double *llr, int64_t B, uint8_t *out,
+                            double *pml, int32_t *winner, uint8_t *passed) {
     const bool list = kind == 7 || kind == 8 || kind == 10 || kind == 12 || kind == 14;
     const bool fast = kind == 9 || kind == 10;
     Code c = make_code(N, K, list ? L : 1, v, frozen, fast ? node_type : nullptr, nullptr, nullptr, 0, nullptr,
@@ -720,7 +772,9 @@ int orc_decode_float(int32_t kind, int32_t N, int32_t K, int32_t L, const int32_
     } else if (kind != 0 && kind != 7 && kind != 8 && kind != 9 && kind != 10) {
         return -3;
     }
+    if (kind != 8 && mask_bits != 0) return -1;
     if (!list) {
+        if (pml || winner || passed) return -1;
         SCDec<FloatDom> dec(c, dom, fast);
         for (int64_t b = 0; b < B; ++b) {
             int rc = dec.run(llr + b * N, out + b * K);
@@ -730,21 +784,20 @@ int orc_decode_float(int32_t kind, int32_t N, int32_t K, int32_t L, const int32_
     }
     SCLDec<FloatDom> dec(c, dom, fast);
     dec.pm_init = kind == 10 ? kInf : 1e300;
-    int ob = K;
     if (kind == 8) {
         if (A < 1 || crc_n < 1 || A + crc_n > K) return -1;
-        dec.ca.A = A;
-        dec.ca.crc_n = crc_n;
-        dec.ca.nchk = crc_n;
-        dec.ca.p.assign(crc_n + 1, 0);
-        for (int i = 0; i < n_loc; ++i) dec.ca.p[crc_loc[i]] = 1;
-        ob = A;
+        if (!set_crc(dec.ca, A, crc_n, crc_n, crc_loc, n_loc, mask, mask_bits)) return -1;
     }
-    for (int64_t b = 0; b < B; ++b) {
-        int rc = dec.run(llr + b * N, out + b * ob);
-        if (rc) return rc;
-    }
-    return 0;
+    return decode_list(dec, llr, N, B, out, kind == 8 ? A : K, pml, winner, passed);
+}
+
+int orc_decode_float(int32_t kind, int32_t N, int32_t K, int32_t L, const int32_t *frozen, const int32_t *node_type,
+                     int32_t v, const double *r_f, const double *r_g, const double *bnd, const int32_t *bnd_off,
+                     const int32_t *bnd_len, const double *rec, const int32_t *rec_off, const int32_t *rec_len,
+                     int32_t A, int32_t crc_n, const int32_t *crc_loc, int32_t n_loc, const double *llr, int64_t B,
+                     uint8_t *out) {
+    return orc_decode_float_status(kind, N, K, L, frozen, node_type, v, r_f, r_g, bnd, bnd_off, bnd_len, rec, rec_off,
+                                   rec_len, A, crc_n, crc_loc, n_loc, nullptr, 0, llr, B, out, nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -103,15 +103,11 @@ def _decode_frame(p, frozen, L, y):
     return ucap[:, n, :][:, np.asarray(frozen) == 0], pml
 
 
-def decode(p, frozen, L, symbols, A=None, crc_n=24, crc_loc=CRC24_LOC, mask=None):
-    """SCL-LUT (A None) or CA-SCL-LUT on symbols [B, N] with the packed tables `p`.
-    Returns (bits [B, K or A], pml [B, L] final path metrics, winner [B] path index,
-    passed [B] bool).  `mask`: 0/1 entries XORed onto the tail of the check code."""
-    assert L <= 8, "stable argsort is the reference's sort only up to 16 entries"
-    frozen = np.asarray(frozen)
+def select(walked, A=None, crc_n=24, crc_loc=CRC24_LOC, mask=None):
+    """The output stage on walked frames [(info [L, K], pml [L])]: SCL-LUT's first minimum (A None) or
+    CA-SCL-LUT's CRC walk in argsort(pml) order.  Returns (bits, pml, winner, passed) as decode."""
     out, pmls, winners, passed = [], [], [], []
-    for y in np.asarray(symbols):
-        info, pml = _decode_frame(p, frozen, L, y)
+    for info, pml in walked:
         if A is None:
             w, ok = int(np.argmin(pml)), False  # argmin: the first minimum
             bits = info[w]
@@ -132,3 +128,12 @@ def decode(p, frozen, L, symbols, A=None, crc_n=24, crc_loc=CRC24_LOC, mask=None
         winners.append(w)
         passed.append(ok)
     return np.stack(out).astype(np.uint8), np.stack(pmls), np.array(winners), np.array(passed, dtype=bool)
+
+
+def decode(p, frozen, L, symbols, A=None, crc_n=24, crc_loc=CRC24_LOC, mask=None):
+    """SCL-LUT (A None) or CA-SCL-LUT on symbols [B, N] with the packed tables `p`.
+    Returns (bits [B, K or A], pml [B, L] final path metrics, winner [B] path index,
+    passed [B] bool).  `mask`: 0/1 entries XORed onto the tail of the check code."""
+    assert L <= 8, "stable argsort is the reference's sort only up to 16 entries"
+    frozen = np.asarray(frozen)
+    return select([_decode_frame(p, frozen, L, y) for y in np.asarray(symbols)], A, crc_n, crc_loc, mask)

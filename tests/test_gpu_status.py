@@ -10,6 +10,15 @@ engine behind the same C-ABI.
 * L = 16 (lane groups of 16) and CA-FastSCL-LUT: the engines against each other,
   and CA-FastSCL-LUT against the plain FastSCL-LUT decoder of the same tables;
 * partial blocks and canaries, optional outputs, the Python call, two streams.
+
+These are fixtures at N = 64 and 128.  Every other status instantiation (the split
+tail at N >= 256, lane groups of 2 .. 16, both pointer-word layouts, the R1L
+twins, the planner's modes, launch seams, the wide generic kernel, the float list
+kinds) is compared with the CPU oracle's status in tests/test_gpu_status_sweep.py.
+There FastSCL-LUT, CA-FastSCL-LUT, L > 8 and float SCL / FastSCL rest on the oracle
+and the host engine agreeing (tests/test_oracle_status.py), not on a recorded
+reference value; SCL-Uniform and SCL-Lloyd, which the host engine does not decode,
+rest on the oracle alone.
 """
 import ctypes
 import glob

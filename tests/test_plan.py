@@ -56,8 +56,7 @@ SWEEP = ([{}, {"sets": 1}, {"sets": 2}, {"pre_chunk": 7}, {"pfx_sets": 1}]
          + [{"lds_budget": b} for b in (256, 2048, 4096, 10240, 65536)])
 
 
-@pytest.fixture(scope="module")
-def harness():
+def load_harness():
     os.makedirs(BUILD, exist_ok=True)
     so = os.path.join(BUILD, "plan_harness.so")
     src = os.path.join(ROOT, "tests", "native", "plan_harness.cpp")
@@ -73,6 +72,11 @@ def harness():
     L.ph_switches_size.restype = ctypes.c_int
     assert L.ph_switches_size() == ctypes.sizeof(Switches)
     return L
+
+
+@pytest.fixture(scope="module")
+def harness():
+    return load_harness()
 
 
 def check(harness, dec, sw):
