@@ -1,2 +1,2 @@
-# Same shape as the reference (PolarBD/PolarBD/__init__.py), without DMetricCalculator.
-from . import CASCLWithRNTI  # noqa: F401
+# Same shape as the reference (PolarBD/PolarBD/__init__.py).
+from . import CASCLWithRNTI, DMetricCalculator  # noqa: F401

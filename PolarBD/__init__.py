@@ -1,6 +1,7 @@
 """Drop-in replacement for the reference package ``PolarBD``
-(PolarEncoder/PolarBD): the same module path and class name for its float CA-SCL
-decoder with RNTI, decoding through libqpd.so.  ``DMetricCalculator`` is not
-provided."""
+(PolarEncoder/PolarBD): the same module paths and class names for its two classes,
+the float CA-SCL decoder with RNTI (``PolarBD.PolarBD.CASCLWithRNTI.CASCLDecoder``)
+and the detection metric (``PolarBD.PolarBD.DMetricCalculator.DMetricCalculator``),
+both through libqpd.so."""
 from . import PolarBD  # noqa: F401
 from quantized_decoder_polar_codes_amd import __version__  # noqa: F401

@@ -286,6 +286,34 @@ int qpd_decode_status(qpd_decoder *dec, const void *d_in, int32_t in_type, int64
 int qpd_decode_status_host(qpd_decoder *dec, const void *h_in, int32_t in_type, int64_t B, uint8_t *h_out,
                            const qpd_status_args *st);
 
+/*
+ * Blind-detection metric (D-metric): the cheap half of PDCCH blind detection, one
+ * double per candidate frame, by which a receiver ranks its candidates before it
+ * runs the list decode above on the best few.  The counterpart of the reference's
+ *     DMetricCalculator::calculate(llr) -> double
+ *         PolarEncoder/PolarBD/_cpp/src/DMetric.cpp:24-177
+ * batched: the float FastSC traversal (FastSCDecoder.cpp:21-151; the same f / g / u,
+ * `<= 0` decisions and SPC rule) plus one accumulator per frame, which starts at 0
+ * (:36) and, in traversal order, adds (sum of the node's LLRs) / size at every R0
+ * node (:57-62) and |sum| / size at every REP node (:91-97), the sums sequential in
+ * element order; R1, SPC and unlabelled nodes and the leaves add nothing.
+ * metric[f] is that double, bit for bit.  (DMetric.cpp's depth -1 case, a labelled
+ * root, cannot arise: qpd_create refuses such a node_type.)
+ *
+ * dec: a QPD_FASTSC_FLOAT decoder -- its frozen_bits and node_type are the
+ * calculator's; QPD_E_INVALID for every other kind (qpd_last_error names it).
+ * llr: float64 [B][N].  metric: float64 [B], required (QPD_E_INVALID if NULL).
+ * out: uint8 [B][K], or NULL for the metric alone; when given it receives exactly
+ * qpd_decode_f64's bits for the same input (the calculator itself returns none).
+ * Device pointers in qpd_dmetric, host pointers in qpd_dmetric_host.  Frames >= B
+ * are never written, in either output.  The refusals return before any launch.
+ * Stream ordering, the per-handle lock and qpd_info.last_engine as for
+ * qpd_decode_f64; the host variant keeps qpd_decode_f64_host's host_max_frames
+ * dispatch (qpd_set_host_engine honoured).
+ */
+int qpd_dmetric(qpd_decoder *dec, const double *d_llr, int64_t B, double *d_metric, uint8_t *d_out, void *stream);
+int qpd_dmetric_host(qpd_decoder *dec, const double *h_llr, int64_t B, double *h_metric, uint8_t *h_out);
+
 /* Returns QPD_E_INPUT (and clears the flags) if any decode since the last
  * check saw a channel symbol outside [0, v), a Lloyd bisect index outside
  * the reconstruction list, or a NaN path metric reaching a list selection

@@ -51,6 +51,8 @@ EXPORTED = (
     "qpd_set_host_engine",
     "qpd_decode_status",
     "qpd_decode_status_host",
+    "qpd_dmetric",
+    "qpd_dmetric_host",
 )
 QPD_KC_PRE, QPD_KC_DECODE, QPD_KC_MC, QPD_KC_PFX, QPD_KC_COUNT = range(5)
 QPD_PROBE_BPERMUTE, QPD_PROBE_READ_B32, QPD_PROBE_READ_B64 = range(3)
@@ -228,6 +230,11 @@ def load():
         L.qpd_decode_status.restype = ctypes.c_int
         L.qpd_decode_status_host.argtypes = [_P, _P, _i32, _i64, _P, ctypes.POINTER(QpdStatusArgs)]
         L.qpd_decode_status_host.restype = ctypes.c_int
+    if not os.environ.get("QPD_LIB") or hasattr(L, "qpd_dmetric"):
+        L.qpd_dmetric.argtypes = [_P, _P, _i64, _P, _P, _P]
+        L.qpd_dmetric.restype = ctypes.c_int
+        L.qpd_dmetric_host.argtypes = [_P, _P, _i64, _P, _P]
+        L.qpd_dmetric_host.restype = ctypes.c_int
     if L.qpd_abi_version() != ABI_VERSION:
         raise ImportError("libqpd.so ABI version mismatch")
     L.qpd_build_id.restype = ctypes.c_char_p

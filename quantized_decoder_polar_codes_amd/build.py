@@ -37,6 +37,8 @@ UNITS = [
     ("qpd_fast_fscl1_st.hip", []),
     ("qpd_fast_fscl16_st.hip", []),
     ("qpd_k_generic.hip", []),
+    # float FastSC with the blind-detection metric (qpd_dmetric)
+    ("qpd_k_generic_dm.hip", []),
     ("qpd_lutgen.cpp", []),
 ]
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Werror=undef"]

@@ -18,6 +18,7 @@
 #include "qpd_probe.hip"
 
 #include "qpd_decoder.hpp"
+#include "qpd_dmetric.hpp"
 #include "qpd_capi_build.hpp"
 #include "qpd_capi_decode.hpp"
 #include "qpd_capi_host.hpp"
@@ -64,6 +65,21 @@ int status_host(qpd_decoder *d, Eng *eng, const In *h_in, int32_t in_type, int64
         if (rq.pass) QPD_HIP(hipMemcpyAsync(rq.pass, dev.pass, (size_t)B, hipMemcpyDeviceToHost, hs));
         return QPD_OK;
     });
+}
+
+// The checks of both D-metric entry points (qpd_dmetric.hpp), before any launch.
+// *run = false where there is nothing to compute (a refusal, or an empty batch).
+int check_dmetric_call(const qpd_decoder *d, int64_t B, const void *in, const void *metric, bool *run) {
+    *run = false;
+    if (!d) return fail(QPD_E_INVALID, "null decoder");
+    std::string err;
+    const int rc = qpd_dm::check(d->pub_kind, metric, err);
+    if (rc) return fail(rc, err);
+    if (B < 0) return fail(QPD_E_INVALID, "negative batch");
+    if (B == 0) return QPD_OK;
+    if (!in) return fail(QPD_E_INVALID, "null buffer");
+    *run = true;
+    return QPD_OK;
 }
 
 }  // namespace
@@ -219,6 +235,36 @@ int qpd_decode_f64_host(qpd_decoder *d, const double *h_llr, int64_t B, uint8_t 
     if (!run) return rc;
     return host_decode(d, d->heng_f64.get(), h_llr, B, h_out,
                        [&](const double *in, uint8_t *out, hipStream_t st) { return decode_f64_impl(d, in, B, out, st); });
+}
+
+int qpd_dmetric(qpd_decoder *d, const double *d_llr, int64_t B, double *d_metric, uint8_t *d_out, void *stream) {
+    bool run;
+    const int rc = check_dmetric_call(d, B, d_llr, d_metric, &run);
+    if (!run) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return ordered(d, st, [&]() { return decode_f64_impl(d, d_llr, B, d_out, st, d_metric); });
+}
+
+int qpd_dmetric_host(qpd_decoder *d, const double *h_llr, int64_t B, double *h_metric, uint8_t *h_out) {
+    bool run;
+    const int rc = check_dmetric_call(d, B, h_llr, h_metric, &run);
+    if (!run) return rc;
+    if (host_engine_takes(d, B)) {
+        std::lock_guard<std::mutex> lk(d->mu);
+        d->last_engine = QPD_RAN_HOST;
+        d->u8_staged = 0;
+        const int32_t flag = qpd_dm::host_run(d->heng_f64.get(), h_llr, B, d->N, d->out_bits, h_metric, h_out);
+        return flag ? input_error(flag) : QPD_OK;
+    }
+    // the GPU: the metrics through a device buffer of the handle, copied back on its
+    // stream before host_roundtrip's synchronization
+    return host_roundtrip(d, h_llr, B, h_out, [&](const double *in, uint8_t *out, hipStream_t hs) -> int {
+        int r = ensure(d->h_st, d->h_st_bytes, (size_t)B * sizeof(double));
+        if (r) return r;
+        if ((r = decode_f64_impl(d, in, B, h_out ? out : nullptr, hs, (double *)d->h_st.p))) return r;
+        QPD_HIP(hipMemcpyAsync(h_metric, d->h_st.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, hs));
+        return QPD_OK;
+    });
 }
 
 int qpd_quantize_llr(qpd_decoder *d, const qpd_mc_channel *ch, const void *d_llr, int32_t llr_type, int64_t B,

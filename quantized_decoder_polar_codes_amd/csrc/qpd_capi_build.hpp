@@ -24,6 +24,7 @@ const void *fast_kernel_fscl(int sets, bool l8, bool r1l);       // qpd_fast_fsc
 const void *fast_kernel_fscl_pw1(int sets, bool l8, bool r1l);   // qpd_fast_fscl1.hip
 const void *fast_kernel_fscl_w16(int sets, bool pw1);            // qpd_fast_fscl16.hip
 const void *generic_kernel(int fam, int dom, bool wide);         // qpd_k_generic.hip
+const void *dmetric_kernel();                                    // qpd_k_generic_dm.hip: float FastSC + D-metric
 // the list kinds' decode-status instantiations (ST), one unit per unit above (*_st.hip)
 const void *fast_kernel_scl_st(int sets, bool l8, bool w16);
 const void *fast_kernel_scl_pw1_st(int sets, bool l8, bool w16);

@@ -64,15 +64,18 @@ void status_at(const qpd_decoder *d, const uint8_t *out, Plan &P) {
     P.st_pass = rq.pass ? rq.pass + f0 : nullptr;
 }
 
+// dmetric (qpd_dmetric, a float FastSC decoder): the launch runs the kernel's DM twin, which writes
+// the frames' blind-detection metrics there and takes a NULL out; the plain kernels do not read it.
 template <class In>
-int launch_generic(qpd_decoder *d, const In *in, int64_t B, uint8_t *out, int grid, hipStream_t st) {
-    const void *kfn = generic_kernel(d->kind, d->dom, d->L > qpd::kMaxL);
+int launch_generic(qpd_decoder *d, const In *in, int64_t B, uint8_t *out, int grid, hipStream_t st,
+                   double *dmetric = nullptr) {
+    const void *kfn = dmetric ? qpd::dmetric_kernel() : generic_kernel(d->kind, d->dom, d->L > qpd::kMaxL);
     if (!kfn) return fail(QPD_E_INVALID, "bad kind");
     qpd::DevPlan P = d->plan;
     P.task_base = d->task_base;
     status_at(d, out, P);
     const In *in_arg = in;
-    void *args[] = {&P, &in_arg, &B, &out};
+    void *args[] = {&P, &in_arg, &B, &out, &dmetric};
     const int rc = timed_launch(d, QPD_KC_DECODE, st, [&]() -> int {
         QPD_HIP(hipLaunchKernel(kfn, dim3(grid), dim3(64), args, 0, st));
         QPD_HIP(hipGetLastError());
@@ -236,12 +239,14 @@ int decode_u8_impl(qpd_decoder *d, const uint8_t *d_symbols, int64_t B, uint8_t 
     return QPD_OK;
 }
 
-int decode_f64_impl(qpd_decoder *d, const double *d_llr, int64_t B, uint8_t *d_out, hipStream_t st) {
+// d_metric: NULL, or qpd_dmetric's output (then d_out may be NULL).
+int decode_f64_impl(qpd_decoder *d, const double *d_llr, int64_t B, uint8_t *d_out, hipStream_t st,
+                    double *d_metric = nullptr) {
     d->last_engine = QPD_RAN_GPU;
     d->u8_staged = 0;
     const int64_t groups = (B + d->plan.fpw - 1) / d->plan.fpw;
     const int grid = (int)std::min<int64_t>(groups, d->max_waves);
-    return launch_generic(d, d_llr, B, d_out, grid, st);
+    return launch_generic(d, d_llr, B, d_out, grid, st, d_metric);
 }
 
 // The checks the decode entry points share.  *run = false where there is

@@ -63,9 +63,10 @@ int host_engine_run(qpd_decoder *d, Eng *eng, const In *h_in, int64_t B, uint8_t
 // H2D copy, decode and D2H copies of the bits and the error word queued on
 // the handle's own stream, one stream synchronization.  (What a per-frame
 // decode(symbols) call of the reference drivers costs here: tools/latency.py.)
+// h_out == NULL (qpd_dmetric_host without bits): no bits are copied back.
 template <class In, class Dec>
 int host_roundtrip(qpd_decoder *d, const In *h_in, int64_t B, uint8_t *h_out, Dec dec) {
-    const size_t in_b = (size_t)B * d->N * sizeof(In), out_b = (size_t)B * d->out_bits;
+    const size_t in_b = (size_t)B * d->N * sizeof(In), out_b = h_out ? (size_t)B * d->out_bits : 0;
     const size_t out_at = (in_b + 15) & ~(size_t)15, err_at = out_at + ((out_b + 15) & ~(size_t)15);
     hipStream_t hs = d->hs;
     return ordered(d, hs, [&]() -> int {
@@ -88,7 +89,7 @@ int host_roundtrip(qpd_decoder *d, const In *h_in, int64_t B, uint8_t *h_out, De
         if (out_b) QPD_HIP(hipMemcpyAsync(pin + out_at, d->h_out.p, out_b, hipMemcpyDeviceToHost, hs));
         QPD_HIP(hipMemcpyAsync(pin + err_at, d->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, hs));
         QPD_HIP(hipStreamSynchronize(hs));
-        std::memcpy(h_out, pin + out_at, out_b);
+        if (out_b) std::memcpy(h_out, pin + out_at, out_b);
         int32_t flag = 0;
         std::memcpy(&flag, pin + err_at, sizeof(flag));
         return take_input_error(d, flag);

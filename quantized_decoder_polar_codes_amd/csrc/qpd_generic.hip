@@ -343,14 +343,28 @@ __device__ __forceinline__ void check_keys(const DevPlan &P, double a, double b)
     }
 }
 
+// 1 / 2^k as a double, exact (k <= kMaxDepth): the divisions by a node's size
+// of the blind-detection metric as products (the same double as the quotient,
+// underflow included, both being the correctly rounded S / 2^k).
+__device__ __forceinline__ double pow2_rcp(int k) { return __longlong_as_double((long long)(1023 - k) << 52); }
+
 // ---------------------------------------------------------------------------
 // The decoders.  KIND = family (SC / SCL / FastSC / FastSCL), DOM = domain.
+// DM (float FastSC only, qpd_k_generic_dm.hip): the blind-detection metric of
+// the reference's DMetricCalculator::calculate (PolarEncoder/PolarBD/_cpp/src/
+// DMetric.cpp:24-177) -- FastSCDecoder.cpp's traversal plus one accumulator per
+// frame, (sum of the node's LLRs) / temp at every R0 node (:57-62) and
+// |sum| / temp at every REP node (:91-97), added in traversal order -- written
+// to dmetric[frame]; out may then be NULL (no re-encode, no bits).  The plain
+// instantiations never read dmetric.
 // ---------------------------------------------------------------------------
-template <int KIND, int DOM, int ML>
+template <int KIND, int DOM, int ML, bool DM = false>
 __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
                                                             const std::conditional_t<DOM == DOM_LUT, int32_t, double>
                                                                 *__restrict__ in,
-                                                            int64_t B, uint8_t *__restrict__ out) {
+                                                            int64_t B, uint8_t *__restrict__ out,
+                                                            double *__restrict__ dmetric) {
+    static_assert(!DM || (KIND == K_FASTSC_LUT && DOM == DOM_FLOAT), "the D-metric is float FastSC's");
     constexpr bool kList = (KIND == K_SCL_LUT || KIND == K_FASTSCL_LUT);
     constexpr bool kLut = DOM == DOM_LUT;
     using In = std::conditional_t<kLut, int32_t, double>;
@@ -378,6 +392,7 @@ __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
         if (!frame_ok) frame = B - 1;
         const In *y = in + frame * (int64_t)N;
         double pm = (gl == 0) ? 0.0 : P.pm_init;
+        double dmet = 0.0;  // DM: DMetric.cpp:36
         PT ps = self, pu = self;
 
         for (int oi = 0; oi < P.nops; ++oi) {
@@ -525,6 +540,12 @@ __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
                                 pm += (double)(float)(l < 0) * fabs(l);
                             }
                         }
+                        if constexpr (DM) {  // DMetric.cpp:57-62: the signed sum, in element order
+#pragma clang fp contract(off)
+                            double S = 0;
+                            for (int j = 0; j < temp; ++j) S += lval(j);
+                            dmet += S * pow2_rcp(n - d);
+                        }
                         for (int w = 0; w < nwo; ++w) store_node_word(P, wsc, d, to_r, w, 0u, lane);
                     } else if (op.type == OP_REP) {
                         uint32_t fill = 0;
@@ -532,6 +553,10 @@ __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
                             double S = 0;
                             for (int j = 0; j < temp; ++j) S += lval(j);
                             fill = S <= 0 ? 0xffffffffu : 0u;
+                            if constexpr (DM) {  // DMetric.cpp:91-97: the same sum again, |.| / temp
+#pragma clang fp contract(off)
+                                dmet += fabs(S) * pow2_rcp(n - d);
+                            }
                         } else {
 #pragma clang fp contract(off)
                             double kk = pm, kf = pm;
@@ -677,6 +702,15 @@ __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
                 }
             }
             wave_sync();  // scratch writes of this op visible to the whole wave
+        }
+
+        if constexpr (DM) {
+            // one lane per frame; the lanes clamped to frame B - 1 do not store
+            if (gl == 0 && frame_ok) dmetric[frame] = dmet;  // DMetric.cpp:177
+            if (!out) {  // wave-uniform: the metric alone, no re-encode and no bits
+                wave_sync();
+                continue;
+            }
         }
 
         // Root partial sums (N bits) are in the own R rows.  u = x F^{(x)n}

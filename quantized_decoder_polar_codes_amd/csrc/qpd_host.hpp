@@ -208,6 +208,14 @@ class Engine {
     double last_metric = 0.0;
     bool last_pass = false;
 
+    // The blind-detection metric (qpd_dmetric_host; float FastSC only): while
+    // want_dmetric is set, a decode also accumulates DMetricCalculator::calculate's
+    // sum (PolarEncoder/PolarBD/_cpp/src/DMetric.cpp:24-177: 0 at :36, an R0 node's
+    // signed LLR sum / temp at :57-62, a REP node's |sum| / temp at :91-97, in
+    // traversal order) into last_dmetric, and a NULL `out` skips the re-encode.
+    bool want_dmetric = false;
+    double last_dmetric = 0.0;
+
     // One frame: y[N] (int32 symbols or float64 LLRs) -> out[out_k].
     // Returns 0, or qpd::ERR_SYMBOL for a channel symbol outside [0, v).
     template <class In>
@@ -225,12 +233,13 @@ class Engine {
             for (int i = 0; i < N; ++i) chan[i] = (T)y[i];
         }
         flags = 0;
+        last_dmetric = 0.0;
         if (P.L == 1)
             run<false>();
         else
             run<true>();
         if (flags) return flags;  // NaN metric: the reference's sort is undefined there, stop
-        finish(out);
+        if (out || !want_dmetric) finish(out);
         return flags;
     }
 
@@ -496,11 +505,17 @@ class Engine {
                         const double l = lv(i, j);
                         pm[i] += (double)(float)(l < 0) * std::fabs(l);  // H5, :90
                     }
+            if (want_dmetric && !list) {  // DMetric.cpp:57-62
+                double s = 0;
+                for (int j = 0; j < temp; ++j) s += lv(0, j);
+                last_dmetric += s / (double)temp;
+            }
             for (int i = 0; i < L; ++i) std::memset(node_out(i, d, to_r), 0, temp);
         } else if (op.type == qpd::OP_REP) {
             if (!list) {
                 double s = 0;
                 for (int j = 0; j < temp; ++j) s += lv(0, j);
+                if (want_dmetric) last_dmetric += std::fabs(s) / (double)temp;  // DMetric.cpp:91-97
                 std::memset(node_out(0, d, to_r), s <= 0 ? 1 : 0, temp);  // H4: `S <= 0`
             } else {
                 for (int i = 0; i < L; ++i) {

@@ -315,6 +315,41 @@ class _DecoderBase:
         _lib.check(fn(self._h, _ptr(a), B, _ptr(out)))
         return out
 
+    # -- blind-detection metric --------------------------------------------------
+    def dmetric_batch(self, llr, return_bits: bool = False):
+        """The blind-detection metric of B frames of LLRs: the reference's
+        ``DMetricCalculator.calculate`` (PolarBD, DMetric.cpp:24-177), batched -- the same
+        double per frame.  ``FastSCDecoder`` only (the metric is its traversal's; the decoder's
+        frozen_bits and node_type are the calculator's); every other class raises TypeError.
+        A torch CUDA float64 tensor [B, N] is read where it is (qpd_dmetric on the current
+        stream, no copy) -> torch CUDA float64 [B]; a numpy array or CPU tensor goes to
+        qpd_dmetric_host -> numpy float64 [B]; other dtypes are converted to float64 as
+        decode_batch converts them.  ``return_bits=True``: ``(metric, bits)``, bits as
+        ``decode_batch(llr)``."""
+        if self._kind != _lib.QPD_FASTSC_FLOAT:
+            raise TypeError(f"dmetric_batch is FastSCDecoder's (the metric is the float FastSC traversal's), "
+                            f"not {type(self).__name__}'s")
+        torch = _torch()
+        lib = _lib.load()
+        if torch is not None and isinstance(llr, torch.Tensor) and llr.is_cuda:
+            xs = llr.reshape(-1, self.N).to(torch.float64).contiguous()
+            B = xs.shape[0]
+            metric = torch.empty(B, dtype=torch.float64, device=xs.device)
+            bits = torch.empty((B, self.out_bits), dtype=torch.uint8, device=xs.device) if return_bits else None
+            stream = torch.cuda.current_stream(xs.device).cuda_stream
+            _lib.check(lib.qpd_dmetric(self._h, ctypes.c_void_p(xs.data_ptr()), B, ctypes.c_void_p(metric.data_ptr()),
+                                       None if bits is None else ctypes.c_void_p(bits.data_ptr()),
+                                       ctypes.c_void_p(stream)))
+            return (metric, bits) if return_bits else metric
+        if torch is not None and isinstance(llr, torch.Tensor):
+            llr = llr.numpy()
+        a = np.ascontiguousarray(np.asarray(llr).astype(np.float64, copy=False).reshape(-1, self.N))
+        B = a.shape[0]
+        metric = np.empty(B, dtype=np.float64)
+        bits = np.empty((B, self.out_bits), dtype=np.uint8) if return_bits else None
+        _lib.check(lib.qpd_dmetric_host(self._h, _ptr(a), B, _ptr(metric), _ptr(bits)))
+        return (metric, bits) if return_bits else metric
+
     # -- LLR input of the LUT decoders ------------------------------------------
     def _llr_args(self, llr, quantizer, name):
         """(device?, contiguous [B, N] array / tensor, llr_type) of an LLR batch."""
