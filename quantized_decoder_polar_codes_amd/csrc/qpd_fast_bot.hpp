@@ -17,6 +17,12 @@ namespace qpd {
 // W2 (bits 0-15, 4 symbols of the current depth n-2 node) | W1 (bits 16-23,
 // 2 symbols) | bL (bit 24, left leaf decision) | c2 (bits 25-26, left result
 // at depth n-1) | c3 (bits 27-30, left result at depth n-2).
+// QPD_BOT3_BYTEIDX: bot3_op holds W3 and W2 in interleaved order (element k in
+// the high nibble of byte k, element k + half in the low one: lut_byte in
+// qpd_fast_lookup.hpp), so byte k is the table index of the lookup one level
+// down as it lies -- as W1's byte is the leaves' since QPD_LEAF_T.  W1, the
+// partial sums and everything stored to rows keep their order; BOTX keeps the
+// element order throughout (bx_spec reads symbols by nibble position).
 // ---------------------------------------------------------------------------
 // Leaf lookups (the depth n-1 node's f / g table, lut4) of the leaf pair whose
 // symbols a, b are nibbles 4, 5 of x1 (and, for g, the left decision u bit 24):
@@ -101,6 +107,7 @@ __device__ __forceinline__ void bot3_op(const FastPlan &P, const Mem (&M)[NS], c
                                         const int32_t *const (&y)[NS], Path (&st)[NS], uint32_t Tf0, uint32_t T2, int gl,
                                         int gbase, int L, int *sel, int sstride, int lane, PF &&prefetch_next,
                                         uint8_t *tb) {
+    constexpr bool BI = QPD_BOT3_BYTEIDX != 0;
     const int p0 = op.tab * QPD_EXP_TABMUL;
     const int fr = op.cnt;
     const uint32_t *ft = P.f_tab, *gt = P.g_tab;
@@ -139,15 +146,24 @@ __device__ __forceinline__ void bot3_op(const FastPlan &P, const Mem (&M)[NS], c
             const int src = gbase + pfield(st[s].ps, op.sh_src);
             const uint32_t a = M[s].ld(sl, op.src_row, src), b = M[s].ld(sl, op.src_row + 1, src);
             const uint32_t ub = (op.flags & MF_BG) ? M[s].ld(ul, op.u_row, gbase + pfield(st[s].U(), op.sh_u)) : 0u;
-            x[s][0] = LT ? lut_lds<8, true>(a, b, ub) : lut_vec<8>(T2, a, b, ub);  // (ub = 0 for f: entries < 256)
+            // (ub = 0 for f: entries < 256); the parent's lookup places W3's nibbles where BOT3 wants them
+            x[s][0] = LT ? lut_lds<8, true, 0, BI>(a, b, ub) : lut_vec<8, BI>(T2, a, b, ub);
         }
     } else {
 #pragma unroll
-        for (int s = 0; s < NS; ++s) x[s][0] = sym_word<CH>(P, M[s], op, y[s], gbase + pfield(st[s].ps, op.sh_src), 0);  // W3
+        for (int s = 0; s < NS; ++s) {
+            x[s][0] = sym_word<CH>(P, M[s], op, y[s], gbase + pfield(st[s].ps, op.sh_src), 0);  // W3
+            if constexpr (BI) x[s][0] = nib_interleave8(x[s][0]);  // from a row / the channel: permuted once
+        }
     }
     // ---- q0 left: W2 = f(W3); q1: W1 = f(W2)
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
+        if constexpr (BI) {
+            const uint32_t w2 = lut_byte<4, true, false>(Tf0, x[s][0]);
+            x[s][1] = w2 | (lut_byte<2, false, false>(Tf12, w2) << 16);
+            continue;
+        }
         const uint32_t w2 = lut_vec<4>(Tf0, x[s][0], x[s][0] >> 16, 0u);
         x[s][1] = w2 | (f_pair(Tf12, 0u, w2) << 16);
     }
@@ -161,6 +177,10 @@ __device__ __forceinline__ void bot3_op(const FastPlan &P, const Mem (&M)[NS], c
 #pragma unroll
     for (int s = 0; s < NS; ++s) {  // q1: W1 = g(W2, c2)
         x[s][1] = (x[s][1] & ~(3u << 25)) | (c[s] << 25);
+        if constexpr (BI) {
+            x[s][1] = (x[s][1] & ~(0xffu << 16)) | (lut_byte<2, false, true>(Tg1, x[s][1], half_bits2(c[s])) << 16);
+            continue;
+        }
         x[s][1] = (x[s][1] & ~(0xffu << 16)) | (g_pair(Tg1, c[s], x[s][1] & 0xffffu) << 16);
     }
     bot_pair<kList, LM, LAZY>(st, x, Tf34, 256, Tg4, Vlo, 32, fr >> 2, gl, gbase, L, lane, sel, sstride, c);  // leaves 2, 3
@@ -173,6 +193,11 @@ __device__ __forceinline__ void bot3_op(const FastPlan &P, const Mem (&M)[NS], c
         const uint32_t c2 = (x[s][1] >> 25) & 3u;
         const uint32_t c3 = (c2 ^ c[s]) | (c[s] << 2);  // combine at depth n-2
         // ---- q0 right: W2 = g(W3, c3); q2: W1 = f(W2)
+        if constexpr (BI) {
+            const uint32_t w2 = lut_byte<4, true, true>(Tg0, x[s][0], half_bits4(c3));
+            x[s][1] = w2 | (lut_byte<2, false, true>(Tf12, w2, 0x8080u) << 16) | (c3 << 27);  // (the second f table)
+            continue;
+        }
         const uint32_t w2 = lut_vec<4>(Tg0, x[s][0], x[s][0] >> 16, c3);
         x[s][1] = w2 | (f_pair(Tf12, 3u, w2) << 16) | (c3 << 27);
     }
@@ -181,6 +206,10 @@ __device__ __forceinline__ void bot3_op(const FastPlan &P, const Mem (&M)[NS], c
 #pragma unroll
     for (int s = 0; s < NS; ++s) {  // q2: W1 = g(W2, c2)
         x[s][1] = (x[s][1] & ~(3u << 25)) | (c[s] << 25);
+        if constexpr (BI) {
+            x[s][1] = (x[s][1] & ~(0xffu << 16)) | (lut_byte<2, false, true>(Tg2, x[s][1], half_bits2(c[s])) << 16);
+            continue;
+        }
         x[s][1] = (x[s][1] & ~(0xffu << 16)) | (g_pair(Tg2, c[s], x[s][1] & 0xffffu) << 16);
     }
     bot_pair<kList, LM, LAZY>(st, x, Tf56, 256, Tg6, Vhi, 32, fr >> 6, gl, gbase, L, lane, sel, sstride, c);  // leaves 6, 7

@@ -1,6 +1,6 @@
 // qpd_fast_lookup.hpp -- the fast engine's table lookups and the ops made of them
 // alone: the re-encode's word steps, the pointer fields, the channel readers,
-// lut_vec / lut_lds, the f / g ops (fg_op, fg_chan_op, ff_op, gsel_op) and the
+// lut_vec / lut_byte / lut_lds, the f / g ops (fg_op, fg_chan_op, ff_op, gsel_op) and the
 // per-op operand prefetch (fetch_pre).
 #pragma once
 #include "qpd_fast_switches.hpp"
@@ -153,7 +153,12 @@ __device__ __forceinline__ uint32_t sym_word(const FastPlan &P, const Mem &M, co
 // one pass each derives the ds_bpermute byte address (idx >> 1, whose bits
 // 7:2 select the dword; + 128 for the upper half) and the nibble offset
 // ((idx & 7) * 4, used by v_bfe through its low 5 bits only).
+// IL (NE = 8, both producers): the results in interleaved order for lut_byte
+// below -- element k at nibble il_nib<8>(k) -- instead of element k at nibble k.
 template <int NE>
+__device__ constexpr int il_nib(int k) { return k < NE / 2 ? 2 * k + 1 : 2 * (k - NE / 2); }
+
+template <int NE, bool IL = false>
 __device__ __forceinline__ uint32_t lut_vec(uint32_t T, uint32_t A, uint32_t B, uint32_t hi) {
     const uint32_t X = ((A << 4) & 0xF0F0F0F0u) | (B & 0x0F0F0F0Fu);
     const uint32_t Y = (A & 0xF0F0F0F0u) | ((B >> 4) & 0x0F0F0F0Fu);
@@ -178,10 +183,56 @@ __device__ __forceinline__ uint32_t lut_vec(uint32_t T, uint32_t A, uint32_t B, 
         const uint32_t WA = (k & 1) ? YA : XA, WS = (k & 1) ? YS : XS;
         // ds_bpermute reads lane (addr >> 2) & 63: the bytes above j need no mask
         const uint32_t v = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(WA >> (8 * j)), (int)T);
-        out |= __builtin_amdgcn_ubfe(v, WS >> (8 * j), 4) << (4 * k);
+        out |= __builtin_amdgcn_ubfe(v, WS >> (8 * j), 4) << (4 * (IL ? il_nib<NE>(k) : k));
 #if QPD_VEC_CHAIN
         if (k + 1 < NE) asm("" : "+v"(out));  // one v_lshl_or per element, not shifts + v_or3
 #endif
+    }
+    return out;
+}
+
+// Interleaved order: a word of NE = 2 / 4 / 8 symbols whose element k (k < NE / 2)
+// sits in the high nibble of byte k and element k + NE / 2 in the low nibble.
+// Byte k is then the table index a * 16 + b of the f / g lookup of elements
+// (k, k + NE / 2) as it lies.  nib_interleave8: a word in element order
+// (nibble i = element i) into that order, one v_perm and a nibble swap.
+__device__ __forceinline__ uint32_t nib_interleave8(uint32_t w) {
+    const uint32_t t = __builtin_amdgcn_perm(w, w, 0x01030002u);  // bytes [e4 e5 | e0 e1 | e6 e7 | e2 e3]
+    return (t & 0xF00FF00Fu) | ((t & 0x00F000F0u) << 4) | ((t >> 4) & 0x00F000F0u);
+}
+
+// Bit k of c -> bit 8k + 7: the table halves of lut_byte's elements from two (c < 4)
+// or four (c < 16) u bits.  One 24-bit multiply (full rate) copies c to distances
+// 7, 14 (, 21, 28 after the shift); no two copies' bits meet, so nothing carries.
+__device__ __forceinline__ uint32_t half_bits2(uint32_t c) { return __umul24(c, 0x4080u) & 0x8080u; }
+__device__ __forceinline__ uint32_t half_bits4(uint32_t c) {
+    uint32_t m = __umul24(c, 0x204081u);
+    asm("" : "+v"(m));  // else the shift is folded into a 32-bit multiply (v_mul_lo_u32: quarter rate)
+    return (m << 7) & 0x80808080u;
+}
+
+// NE = 2 or 4 lookups T[byte k of W] (QPD_BOT3_BYTEIDX: BOT3's internal nodes),
+// W in interleaved order: no index build.  The ds_bpermute address of element k
+// is bits 8k+1 .. 8k+7 (the low two address bits are ignored), with H (HAS_H: bit
+// 8k + 7 = the table half of element k -- the g table's u = 1 half, or the second
+// of two packed f tables) put above the index once for the word; the nibble
+// offset is (byte & 7) * 4, masked once for the word (v_bfe reads its low five
+// bits).  IL: the results in interleaved order again (NE = 4: W2 from W3), else
+// element k at nibble k (NE = 2: the leaf pair's W1 as leaf_idx reads it).
+// Bits of W above byte NE - 1 are ignored.
+template <int NE, bool IL, bool HAS_H>
+__device__ __forceinline__ uint32_t lut_byte(uint32_t T, uint32_t W, uint32_t H = 0u) {
+    constexpr uint32_t M7 = NE == 4 ? 0x7F7F7F7Fu : 0x7F7Fu, M3 = NE == 4 ? 0x1C1C1C1Cu : 0x1C1Cu;
+    const uint32_t WS = (W << 2) & M3;
+    uint32_t WA = 0;
+    if constexpr (HAS_H) WA = ((W >> 1) & M7) | (H & ~M7);
+    uint32_t out = 0;
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {
+        // (HAS_H: ds_bpermute reads lane (addr >> 2) & 63, the bytes above k need no mask)
+        const uint32_t addr = HAS_H ? WA >> (8 * k) : __builtin_amdgcn_ubfe(W, 8 * k + 1, 7);
+        const uint32_t v = (uint32_t)__builtin_amdgcn_ds_bpermute((int)addr, (int)T);
+        out |= __builtin_amdgcn_ubfe(v, WS >> (8 * k), 4) << (4 * (IL ? il_nib<NE>(k) : k));
     }
     return out;
 }
@@ -215,7 +266,7 @@ __device__ __forceinline__ int gtab_dw(int lane) { return lane ^ ((lane >> 5) * 
 // kernel declares no static LDS before them): the lookups address LDS through a
 // constant, which the compiler folds into each ds_read_u8's offset field.
 typedef __attribute__((address_space(3))) const uint8_t lds_u8;
-template <int NE, bool ISG, int TOFF = 0>
+template <int NE, bool ISG, int TOFF = 0, bool IL = false>
 __device__ __forceinline__ uint32_t lut_lds(uint32_t A, uint32_t B, uint32_t hi) {
     lds_u8 *const tb = (lds_u8 *)(size_t)TOFF;
     uint32_t X = ((A << 4) & 0xF0F0F0F0u) | (B & 0x0F0F0F0Fu);
@@ -262,9 +313,13 @@ __device__ __forceinline__ uint32_t lut_lds(uint32_t A, uint32_t B, uint32_t hi)
         // shift per element and an or3 per two.  O passes through an empty asm so
         // that the compiler does not distribute the final shift over O's two
         // halves (v_lshlrev x2 + v_or3 instead of one v_lshl_or: +1 VALU per word).
+        // IL (interleaved order, see lut_byte): the low nibbles are elements 4-7, the
+        // high ones elements 0-3 -- only which loaded bytes are paired changes.
         typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-        const u16x2 r0 = {tb[idx[0]], tb[idx[4]]}, r1 = {tb[idx[2]], tb[idx[6]]};
-        const u16x2 s0 = {tb[idx[1]], tb[idx[5]]}, s1 = {tb[idx[3]], tb[idx[7]]};
+        constexpr int e0 = IL ? 4 : 0, e1 = IL ? 6 : 4, e2 = IL ? 5 : 2, e3 = IL ? 7 : 6;
+        constexpr int o0 = IL ? 0 : 1, o1 = IL ? 2 : 5, o2 = IL ? 1 : 3, o3 = IL ? 3 : 7;
+        const u16x2 r0 = {tb[idx[e0]], tb[idx[e1]]}, r1 = {tb[idx[e2]], tb[idx[e3]]};
+        const u16x2 s0 = {tb[idx[o0]], tb[idx[o1]]}, s1 = {tb[idx[o2]], tb[idx[o3]]};
         const uint32_t E = __builtin_bit_cast(uint32_t, r0) | (__builtin_bit_cast(uint32_t, r1) << 8);
         uint32_t O = __builtin_bit_cast(uint32_t, s0) | (__builtin_bit_cast(uint32_t, s1) << 8);
 #if QPD_LUT_OPAQUE
@@ -275,7 +330,7 @@ __device__ __forceinline__ uint32_t lut_lds(uint32_t A, uint32_t B, uint32_t hi)
 #endif
     uint32_t out = 0;
 #pragma unroll
-    for (int k = 0; k < NE; ++k) out |= (uint32_t)tb[idx[k]] << (4 * k);
+    for (int k = 0; k < NE; ++k) out |= (uint32_t)tb[idx[k]] << (4 * (IL ? il_nib<NE>(k) : k));
     return out;
 }
 

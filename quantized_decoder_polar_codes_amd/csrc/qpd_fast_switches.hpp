@@ -70,6 +70,13 @@
 #ifndef QPD_BOT3_LAZY
 #define QPD_BOT3_LAZY 1  // bot3_op: each stage issues the loads of the next (the list kinds; +0.5 % SCL-LUT at 5 waves, r04h)
 #endif
+// QPD_BOT3_BYTEIDX: bot3_op keeps W3 and W2 in interleaved order and looks its 12
+// internal symbols up by the bytes as they lie (lut_byte, qpd_fast_lookup.hpp)
+// instead of six lut_vec index builds per subtree and set.  Static count and
+// A/B: profiles/AB_RECORDS.md, `bot3_byteidx_ab.jsonl`.
+#ifndef QPD_BOT3_BYTEIDX
+#define QPD_BOT3_BYTEIDX 1
+#endif
 #ifndef QPD_SPEC_ROT
 #define QPD_SPEC_ROT 1  // special ops: one code copy, the sets rotated through slot 0 (else unrolled)
 #endif
