@@ -54,6 +54,8 @@ def lib():
         L.orc_decode_float_status.argtypes = [i32, i32, i32, i32, P, P, i32, P, P, P, P, P, P, P, P, i32, i32, P, i32,
                                               P, i32, P, i64, P, P, P, P]
         L.orc_decode_float_status.restype = ctypes.c_int
+        L.orc_float_edge_counts.argtypes = [P]
+        L.orc_float_edge_counts.restype = None
         _lib = L
     return _lib
 
@@ -213,6 +215,18 @@ def _decode_float(kind, N, K, frozen, llr, L, node_type, quant, A, crc_n, crc_lo
     if rc != 0:
         raise RuntimeError(f"oracle decode failed rc={rc}")
     return (out, pml, winner.astype(np.int64), passed.astype(bool)) if status else out
+
+
+EDGE_COUNTERS = ("clip_equal", "quotient_integral", "bisect_equal", "first_cell", "last_cell")
+
+
+def float_edge_counts() -> dict:
+    """How often the float re-quantizers met a cell edge since the last call (then cleared): the uniform clip
+    comparison with |x| == M, an integral quotient x / r, a Lloyd probe with boundary == x, and the first / last
+    cell taken (uniform: the negative / positive clip)."""
+    out = np.zeros(len(EDGE_COUNTERS), dtype=np.int64)
+    lib().orc_float_edge_counts(_ptr(out))
+    return dict(zip(EDGE_COUNTERS, out.tolist()))
 
 
 def reference_module():

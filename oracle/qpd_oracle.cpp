@@ -174,6 +174,15 @@ struct LutDom {
 
 enum Quant { Q_NONE = 0, Q_UNIFORM = 1, Q_LLOYD = 2 };
 
+// How often the re-quantizers met the edges of their cells since the last orc_float_edge_counts: the
+// clip comparison with |x| == M and the quotient x / r an integer (uniform), a probe b[mid] == x (Lloyd),
+// and the first / last cell taken (uniform: the negative / positive clip).  Counted for the tests that
+// show their inputs reach these edges (tests/test_float_oracle_masks_quant.py); not thread-safe.
+struct EdgeCounts {
+    int64_t clip_equal, quotient_integral, bisect_equal, first_cell, last_cell;
+};
+EdgeCounts g_edges = {0, 0, 0, 0, 0};
+
 struct FloatDom {
     using T = double;
     int quant = Q_NONE;
@@ -187,6 +196,13 @@ struct FloatDom {
     mutable bool ub = false;  // a Lloyd index outside the reconstruction (reference UB)
 
     static double Q(double x, double r, double M) {  // utils.cpp:8-10
+        const double q = x / r;
+        g_edges.clip_equal += std::fabs(x) == M;
+        if (std::fabs(x) > M) {
+            ++(x < 0 ? g_edges.first_cell : g_edges.last_cell);
+        } else {
+            g_edges.quotient_integral += q == std::floor(q);
+        }
         return std::fabs(x) > M ? sgn(x) * (M - 0.5 * r) : (std::floor(x / r) + 0.5) * r;
     }
     double bisect(double a, int t, int posi) const {  // utils.cpp:12-24
@@ -194,6 +210,7 @@ struct FloatDom {
         int lo = 0, hi = bnd_len[t * nodes + posi];
         while (lo < hi) {
             int mid = (lo + hi) / 2;
+            g_edges.bisect_equal += b[mid] == a;
             if (b[mid] < a)
                 lo = mid + 1;
             else
@@ -203,6 +220,8 @@ struct FloatDom {
             ub = true;
             return 0.0;
         }
+        g_edges.first_cell += lo - 1 == 0;
+        g_edges.last_cell += lo - 1 == rec_len[t * nodes + posi] - 1;
         return rec[rec_off[t * nodes + posi] + lo - 1];
     }
     T f(int posi, int, T a, T b) const {
@@ -789,6 +808,14 @@ int orc_decode_float_status(int32_t kind, int32_t N, int32_t K, int32_t L, const
         if (!set_crc(dec.ca, A, crc_n, crc_n, crc_loc, n_loc, mask, mask_bits)) return -1;
     }
     return decode_list(dec, llr, N, B, out, kind == 8 ? A : K, pml, winner, passed);
+}
+
+// Copies the five counters of EdgeCounts (in its order) to out and clears them.
+void orc_float_edge_counts(int64_t *out) {
+    const int64_t v[5] = {g_edges.clip_equal, g_edges.quotient_integral, g_edges.bisect_equal, g_edges.first_cell,
+                          g_edges.last_cell};
+    for (int i = 0; i < 5; ++i) out[i] = v[i];
+    g_edges = EdgeCounts{0, 0, 0, 0, 0};
 }
 
 int orc_decode_float(int32_t kind, int32_t N, int32_t K, int32_t L, const int32_t *frozen, const int32_t *node_type,
