@@ -333,6 +333,12 @@ int qpd_check_input_error(qpd_decoder *dec);
  * CRC-aided kinds the message is A random bits followed by the first K-A bits
  * of their CRC (the driver's CRCEnc, mainQuantizedDecoder_LLRDomain.py:153-156),
  * and d_msg holds the A message bits ([B][A]).
+ * Alignment of d_msg (all four qpd_mc_* entry points): where a row is a
+ * multiple of 8 bytes (K % 8 == 0, or A % 8 == 0 for the CRC-aided kinds) the
+ * generator stores it 8 bytes at a time and d_msg must be 8-byte aligned --
+ * QPD_E_INVALID otherwise, before anything is launched; any other row length
+ * takes any base.  d_out takes any base (the counters of d_counts fall back to
+ * a byte loop).
  */
 typedef struct qpd_mc_channel {
     double sigma;           /* AWGN standard deviation                 */

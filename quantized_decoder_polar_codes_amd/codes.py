@@ -155,8 +155,8 @@ def quantize_channel(llr: np.ndarray, interval_x: np.ndarray, channel_lut: np.nd
     lut = np.asarray(channel_lut).reshape(-1)
     idx = np.searchsorted(edges[:-1], llr, side="left")  # == bisect_left
     out = lut[np.clip(idx - 1, 0, len(lut) - 1)].astype(np.int32)
-    out = np.where(llr <= edges[0], 0, out)
     out = np.where(llr >= edges[-1], q_channel - 1, out)
+    out = np.where(llr <= edges[0], 0, out)  # tested first by the driver: it wins where edges[0] == edges[-1]
     return out.astype(np.int32)
 
 

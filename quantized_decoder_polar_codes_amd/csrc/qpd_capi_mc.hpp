@@ -22,6 +22,14 @@ int check_channel(const qpd_mc_channel *ch) {
     return QPD_OK;
 }
 
+// d_msg's alignment (include/qpd.h): rows of a multiple of 8 message bits are
+// stored 8 bytes at a time (mc_frames_kernel), so their base is 8-byte aligned.
+int check_msg_alignment(const qpd_decoder *d, const void *d_msg) {
+    if ((d->out_bits & 7) == 0 && ((uintptr_t)d_msg & 7u) != 0)
+        return fail(QPD_E_INVALID, "d_msg alignment: rows of a multiple of 8 message bits need an 8-byte aligned base");
+    return QPD_OK;
+}
+
 // The LLR entry points' channel.  Without rec the quantizer is unused (edges /
 // lut may be null, n_edges 0): only sigma counts.  With rec: a whole channel
 // quantizer, and one finite reconstruction value per symbol (the generator
@@ -51,6 +59,7 @@ int check_mc_llr_args(const qpd_decoder *d, const qpd_mc_channel *ch, const doub
     if (B < 0 || frame0 < 0) return fail(QPD_E_INVALID, "negative frame range");
     if (B == 0) return QPD_OK;
     if (!d_msg || !d_buf) return fail(QPD_E_INVALID, "null buffer");
+    if (check_msg_alignment(d, d_msg)) return QPD_E_INVALID;
     const int rc = check_llr_channel(ch, rec);
     *run = !rc;
     return rc;
@@ -68,6 +77,7 @@ int check_mc_args(const qpd_decoder *d, const qpd_mc_channel *ch, bool lut_only,
     if (B < 0 || frame0 < 0) return fail(QPD_E_INVALID, "negative frame range");
     if (B == 0) return QPD_OK;
     if (!d_msg || !d_buf) return fail(QPD_E_INVALID, "null buffer");
+    if (check_msg_alignment(d, d_msg)) return QPD_E_INVALID;
     const int rc = check_channel(ch);
     *run = !rc;
     return rc;

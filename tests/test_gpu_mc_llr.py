@@ -237,6 +237,13 @@ def test_refusals(env):
     for name, buf in (("qpd_mc_llr", llr), ("qpd_mc_decode_f64", out)):
         rc, why = _call(env, name, ca, ch, None, B, msg, buf)
         assert rc == L.QPD_E_UNSUPPORTED and why
+    # d_msg off the 8-byte grid with rows of a multiple of 8 bits (K = 64): refused before any launch
+    # (include/qpd.h; the generator stores such rows 8 bytes at a time)
+    fresh, _ = _float_decoder(env, "SC", N, K)
+    for name, buf in (("qpd_mc_llr", llr), ("qpd_mc_decode_f64", out)):
+        rc, why = _call(env, name, fresh, ch, None, B, msg.view(-1)[1:], buf)
+        assert rc == L.QPD_E_INVALID and "alignment" in why
+        assert fresh.info()["last_engine"] == L.QPD_RAN_NONE
     # an empty range: QPD_OK, nothing written (no quantizer needed without rec)
     torch.cuda.synchronize()
     msg.fill_(9), out.fill_(9), llr.fill_(-2.5)
