@@ -287,6 +287,51 @@ int qpd_decode_status_host(qpd_decoder *dec, const void *h_in, int32_t in_type, 
                            const qpd_status_args *st);
 
 /*
+ * List output: all L candidates of a list decode, not only the output path -- for
+ * blind detection without one decode per candidate RNTI (test any number of RNTIs
+ * on the candidates' K bits; an unknown mask is CRC(info) XOR tail), for genie list
+ * bounds ("was the sent word in the list?") and for re-ranking by the caller.  The
+ * reference keeps these paths to the end of CASCLLUTDecoder.cpp:264-302 and drops
+ * them.
+ *
+ * Candidate r of frame f is the path at position r of the reference's
+ * argsort(PML): metric ascending, ties by list slot (the stable order libstdc++'s
+ * sort gives for L <= 16) -- for every list kind, CRC-aided or not.
+ *   cand_bits[f][r][t]  the path's decision at information position info_pos[t],
+ *                       t < K: for the CRC-aided kinds all K bits, message and CRC
+ *                       tail; for the Fast kinds after the re-encode, as the output
+ *                       bits are.  Required (QPD_E_INVALID if NULL).
+ *   cand_metric[f][r]   that path's own final PML double; or NULL.
+ *   cand_pass[f][r]     that path's CRC compare under crc_mask (the compare of
+ *                       qpd_status_args.crc_pass); CRC-aided kinds only
+ *                       (QPD_E_INVALID otherwise); or NULL.
+ *   chosen[f]           the r of the path whose bits d_out receives: the first
+ *                       passing r for the CRC-aided kinds, else 0; or NULL.
+ * d_out / h_out may be NULL; when given it receives exactly qpd_decode_status's
+ * bits.  crc_mask, in_type, stream ordering, the error word and the host variant's
+ * dispatch: as qpd_decode_status / _host.  The outputs are device pointers in
+ * qpd_decode_list, host pointers in qpd_decode_list_host.  Frames >= B are never
+ * written.
+ * Refused before any launch: the SC / FastSC kinds, cand_pass or mask bits on a
+ * kind without CRC, cand_bits NULL (QPD_E_INVALID); L = 1 (QPD_E_UNSUPPORTED); and
+ * L > 16 (QPD_E_UNSUPPORTED): there the reference's argsort is libstdc++'s
+ * unstable introsort, and the first-minimum output path of the kinds without CRC
+ * need not be candidate 0.
+ */
+typedef struct qpd_list_args {
+    const uint8_t *crc_mask;   /* host, [crc_mask_bits] of 0/1, or NULL (as qpd_status_args) */
+    int32_t crc_mask_bits;     /* 0..crc_n                                                    */
+    uint8_t *cand_bits;        /* [B][L][K]  required                                         */
+    double  *cand_metric;      /* [B][L]     or NULL                                          */
+    uint8_t *cand_pass;        /* [B][L]     or NULL; CRC-aided kinds only                    */
+    int32_t *chosen;           /* [B]        or NULL                                          */
+} qpd_list_args;
+int qpd_decode_list(qpd_decoder *dec, const void *d_in, int32_t in_type, int64_t B, uint8_t *d_out,
+                    const qpd_list_args *ls, void *stream);
+int qpd_decode_list_host(qpd_decoder *dec, const void *h_in, int32_t in_type, int64_t B, uint8_t *h_out,
+                         const qpd_list_args *ls);
+
+/*
  * Blind-detection metric (D-metric): the cheap half of PDCCH blind detection, one
  * double per candidate frame, by which a receiver ranks its candidates before it
  * runs the list decode above on the best few.  The counterpart of the reference's

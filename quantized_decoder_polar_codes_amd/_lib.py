@@ -51,6 +51,8 @@ EXPORTED = (
     "qpd_set_host_engine",
     "qpd_decode_status",
     "qpd_decode_status_host",
+    "qpd_decode_list",
+    "qpd_decode_list_host",
     "qpd_dmetric",
     "qpd_dmetric_host",
 )
@@ -121,6 +123,17 @@ class QpdStatusArgs(ctypes.Structure):
         ("crc_mask_bits", _i32),
         ("metric", _P),
         ("crc_pass", _P),
+    ]
+
+
+class QpdListArgs(ctypes.Structure):
+    _fields_ = [
+        ("crc_mask", _P),
+        ("crc_mask_bits", _i32),
+        ("cand_bits", _P),
+        ("cand_metric", _P),
+        ("cand_pass", _P),
+        ("chosen", _P),
     ]
 
 
@@ -230,6 +243,11 @@ def load():
         L.qpd_decode_status.restype = ctypes.c_int
         L.qpd_decode_status_host.argtypes = [_P, _P, _i32, _i64, _P, ctypes.POINTER(QpdStatusArgs)]
         L.qpd_decode_status_host.restype = ctypes.c_int
+    if not os.environ.get("QPD_LIB") or hasattr(L, "qpd_decode_list"):
+        L.qpd_decode_list.argtypes = [_P, _P, _i32, _i64, _P, ctypes.POINTER(QpdListArgs), _P]
+        L.qpd_decode_list.restype = ctypes.c_int
+        L.qpd_decode_list_host.argtypes = [_P, _P, _i32, _i64, _P, ctypes.POINTER(QpdListArgs)]
+        L.qpd_decode_list_host.restype = ctypes.c_int
     if not os.environ.get("QPD_LIB") or hasattr(L, "qpd_dmetric"):
         L.qpd_dmetric.argtypes = [_P, _P, _i64, _P, _P, _P]
         L.qpd_dmetric.restype = ctypes.c_int

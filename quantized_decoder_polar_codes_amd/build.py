@@ -36,9 +36,17 @@ UNITS = [
     ("qpd_fast_fscl_st.hip", []),
     ("qpd_fast_fscl1_st.hip", []),
     ("qpd_fast_fscl16_st.hip", []),
+    # ... and with the list-output tail (qpd_decode_list)
+    ("qpd_k_scl_ls.hip", []),
+    ("qpd_k_scl1_ls.hip", []),
+    ("qpd_fast_fscl_ls.hip", []),
+    ("qpd_fast_fscl1_ls.hip", []),
+    ("qpd_fast_fscl16_ls.hip", []),
     ("qpd_k_generic.hip", []),
     # float FastSC with the blind-detection metric (qpd_dmetric)
     ("qpd_k_generic_dm.hip", []),
+    # the generic engine's list kinds with the list-output tail (qpd_decode_list)
+    ("qpd_k_generic_ls.hip", []),
     ("qpd_lutgen.cpp", []),
 ]
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Werror=undef"]

@@ -67,6 +67,64 @@ int status_host(qpd_decoder *d, Eng *eng, const In *h_in, int32_t in_type, int64
     });
 }
 
+// The checks of both list entry points: the request (qpd_list.hpp), then the decode's
+// own, with the bits optional.
+int check_list_call(const qpd_decoder *d, int32_t in_type, const qpd_list_args *la, const char *suffix, int64_t B,
+                    const void *in, qpd_list::Req *rq, bool *run) {
+    *run = false;
+    if (!d) return fail(QPD_E_INVALID, "null decoder");
+    std::string err;
+    const int rc = qpd_list::check(d->pub_kind, d->L, d->crc_n, in_type, la, rq, err);
+    if (rc) return fail(rc, err);
+    return check_decode_args(d, in_type != QPD_IN_F64, suffix, B, in, rq->bits, run);
+}
+
+// One device-buffer list decode (caller: lock held, stream ordered): into d_out, or
+// into a buffer of the handle where the call gave none (a launch finds its first
+// frame from where it writes its bits, list_at).
+int decode_list_typed(qpd_decoder *d, const void *d_in, int32_t in_type, int64_t B, uint8_t *d_out,
+                      const qpd_list::Req &rq, hipStream_t st) {
+    if (!d_out) {
+        const int rc = ensure(d->ls_out, d->ls_out_bytes, (size_t)B * d->out_bits);
+        if (rc) return rc;
+        d_out = (uint8_t *)d->ls_out.p;
+    }
+    ListScope sc(d, rq, d_out);
+    return decode_typed(d, d_in, in_type, B, d_out, st);
+}
+
+template <class Eng, class In>
+int list_host(qpd_decoder *d, Eng *eng, const In *h_in, int32_t in_type, int64_t B, uint8_t *h_out,
+              const qpd_list::Req &rq) {
+    if (host_engine_takes(d, B)) {
+        std::lock_guard<std::mutex> lk(d->mu);
+        d->last_engine = QPD_RAN_HOST;
+        d->u8_staged = 0;
+        const int32_t flag = qpd_list::host_run(eng, h_in, B, d->N, d->K, d->L, d->out_bits, h_out, rq);
+        return flag ? input_error(flag) : QPD_OK;
+    }
+    // the GPU: the list through a device buffer of the handle (metrics, chosen, bits,
+    // flags: each aligned for its type), copied back on its stream before
+    // host_roundtrip's synchronization
+    const size_t n = (size_t)B * d->L, nb = n * d->K;
+    return host_roundtrip(d, h_in, B, h_out, [&](const In *in, uint8_t *out, hipStream_t hs) -> int {
+        int rc = ensure(d->h_ls, d->h_ls_bytes, n * 8 + (size_t)B * 4 + nb + n);
+        if (rc) return rc;
+        char *base = (char *)d->h_ls.p;
+        qpd_list::Req dev = rq;
+        dev.bits = (uint8_t *)(base + n * 8 + (size_t)B * 4);
+        if (rq.metric) dev.metric = (double *)base;
+        if (rq.chosen) dev.chosen = (int32_t *)(base + n * 8);
+        if (rq.pass) dev.pass = dev.bits + nb;
+        if ((rc = decode_list_typed(d, in, in_type, B, h_out ? out : nullptr, dev, hs))) return rc;  // (no h_out: no staging for it)
+        QPD_HIP(hipMemcpyAsync(rq.bits, dev.bits, nb, hipMemcpyDeviceToHost, hs));
+        if (rq.metric) QPD_HIP(hipMemcpyAsync(rq.metric, dev.metric, n * 8, hipMemcpyDeviceToHost, hs));
+        if (rq.pass) QPD_HIP(hipMemcpyAsync(rq.pass, dev.pass, n, hipMemcpyDeviceToHost, hs));
+        if (rq.chosen) QPD_HIP(hipMemcpyAsync(rq.chosen, dev.chosen, (size_t)B * 4, hipMemcpyDeviceToHost, hs));
+        return QPD_OK;
+    });
+}
+
 // The checks of both D-metric entry points (qpd_dmetric.hpp), before any launch.
 // *run = false where there is nothing to compute (a refusal, or an empty batch).
 int check_dmetric_call(const qpd_decoder *d, int64_t B, const void *in, const void *metric, bool *run) {
@@ -199,6 +257,29 @@ int qpd_decode_status_host(qpd_decoder *d, const void *h_in, int32_t in_type, in
         case QPD_IN_I32: return status_host(d, d->heng_lut.get(), (const int32_t *)h_in, in_type, B, h_out, rq);
         case QPD_IN_U8: return status_host(d, d->heng_lut.get(), (const uint8_t *)h_in, in_type, B, h_out, rq);
         default: return status_host(d, d->heng_f64.get(), (const double *)h_in, in_type, B, h_out, rq);
+    }
+}
+
+int qpd_decode_list(qpd_decoder *d, const void *d_in, int32_t in_type, int64_t B, uint8_t *d_out,
+                    const qpd_list_args *la, void *stream) {
+    bool run;
+    qpd_list::Req rq;
+    const int rc = check_list_call(d, in_type, la, "", B, d_in, &rq, &run);
+    if (!run) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return ordered(d, st, [&]() { return decode_list_typed(d, d_in, in_type, B, d_out, rq, st); });
+}
+
+int qpd_decode_list_host(qpd_decoder *d, const void *h_in, int32_t in_type, int64_t B, uint8_t *h_out,
+                         const qpd_list_args *la) {
+    bool run;
+    qpd_list::Req rq;
+    const int rc = check_list_call(d, in_type, la, "_host", B, h_in, &rq, &run);
+    if (!run) return rc;
+    switch (in_type) {
+        case QPD_IN_I32: return list_host(d, d->heng_lut.get(), (const int32_t *)h_in, in_type, B, h_out, rq);
+        case QPD_IN_U8: return list_host(d, d->heng_lut.get(), (const uint8_t *)h_in, in_type, B, h_out, rq);
+        default: return list_host(d, d->heng_f64.get(), (const double *)h_in, in_type, B, h_out, rq);
     }
 }
 

@@ -24,6 +24,7 @@ const void *fast_kernel_fscl(int sets, bool l8, bool r1l);       // qpd_fast_fsc
 const void *fast_kernel_fscl_pw1(int sets, bool l8, bool r1l);   // qpd_fast_fscl1.hip
 const void *fast_kernel_fscl_w16(int sets, bool pw1);            // qpd_fast_fscl16.hip
 const void *generic_kernel(int fam, int dom, bool wide);         // qpd_k_generic.hip
+const void *generic_list_kernel(int fam, int dom, bool wide);    // qpd_k_generic_ls.hip: list kinds + list output
 const void *dmetric_kernel();                                    // qpd_k_generic_dm.hip: float FastSC + D-metric
 // the list kinds' decode-status instantiations (ST), one unit per unit above (*_st.hip)
 const void *fast_kernel_scl_st(int sets, bool l8, bool w16);
@@ -31,6 +32,12 @@ const void *fast_kernel_scl_pw1_st(int sets, bool l8, bool w16);
 const void *fast_kernel_fscl_st(int sets, bool l8, bool r1l);
 const void *fast_kernel_fscl_pw1_st(int sets, bool l8, bool r1l);
 const void *fast_kernel_fscl_w16_st(int sets, bool pw1);
+// ... and their list-output instantiations (LIST, the *_ls.hip units)
+const void *fast_kernel_scl_ls(int sets, bool l8, bool w16);
+const void *fast_kernel_scl_pw1_ls(int sets, bool l8, bool w16);
+const void *fast_kernel_fscl_ls(int sets, bool l8, bool r1l);
+const void *fast_kernel_fscl_pw1_ls(int sets, bool l8, bool r1l);
+const void *fast_kernel_fscl_w16_ls(int sets, bool pw1);
 }  // namespace qpd
 
 namespace {
@@ -39,7 +46,18 @@ using qpd_sched::Schedule;
 
 // The decode kernel instantiation of a plan (nullptr: none, the launch fails).
 // pw1: the op list's pointer fields fit one word (compact_pointer_fields).
-const void *fast_kernel(int kind, int sets, bool l8, bool r1l, bool pw1, bool w16, bool st = false) {
+// st: 0 the plain kernel, 1 its ST twin, 2 its LIST twin.
+const void *fast_kernel(int kind, int sets, bool l8, bool r1l, bool pw1, bool w16, int st = 0) {
+    if (st == 2) {  // the same plan's kernel with the list-output tail (list kinds)
+        switch (kind) {
+            case QPD_SCL_LUT:
+                return r1l ? nullptr : pw1 ? qpd::fast_kernel_scl_pw1_ls(sets, l8, w16) : qpd::fast_kernel_scl_ls(sets, l8, w16);
+            case QPD_FASTSCL_LUT:
+                if (w16) return r1l ? nullptr : qpd::fast_kernel_fscl_w16_ls(sets, pw1);
+                return pw1 ? qpd::fast_kernel_fscl_pw1_ls(sets, l8, r1l) : qpd::fast_kernel_fscl_ls(sets, l8, r1l);
+            default: return nullptr;
+        }
+    }
     if (st) {  // the same plan's kernel with the decode-status tail (list kinds)
         switch (kind) {
             case QPD_SCL_LUT:
@@ -283,9 +301,14 @@ int build_fast(qpd_decoder *d, const qpd_config *c, const Schedule &s) {
     if (!kfn) return fail(QPD_E_UNSUPPORTED, "fast plan: no decode kernel instantiation for this plan");
     if ((rc = check_no_static_lds(kfn, "fast decode kernel"))) return rc;
     if (d->kind == QPD_SCL_LUT || d->kind == QPD_FASTSCL_LUT) {  // qpd_decode_status runs the plan's ST twin
-        const void *ksfn = fast_kernel(d->kind, d->sets, d->l8, d->r1l, d->pw1, d->w16, true);
+        const void *ksfn = fast_kernel(d->kind, d->sets, d->l8, d->r1l, d->pw1, d->w16, 1);
         if (!ksfn) return fail(QPD_E_UNSUPPORTED, "fast plan: no decode-status kernel instantiation for this plan");
         if ((rc = check_no_static_lds(ksfn, "fast decode-status kernel"))) return rc;
+        if (d->L > 1 && d->L <= qpd_list::kMaxListOut) {  // ... and qpd_decode_list its LIST twin
+            const void *klfn = fast_kernel(d->kind, d->sets, d->l8, d->r1l, d->pw1, d->w16, 2);
+            if (!klfn) return fail(QPD_E_UNSUPPORTED, "fast plan: no list-output kernel instantiation for this plan");
+            if ((rc = check_no_static_lds(klfn, "fast list-output kernel"))) return rc;
+        }
     }
     // (the prefix stages' two-set instantiations do the same offset-0 byte-table lookups)
     if (d->pfx[0].nops > 0 && d->pfx_sets == 2 &&

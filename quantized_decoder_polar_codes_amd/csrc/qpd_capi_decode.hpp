@@ -64,16 +64,38 @@ void status_at(const qpd_decoder *d, const uint8_t *out, Plan &P) {
     P.st_pass = rq.pass ? rq.pass + f0 : nullptr;
 }
 
+// Likewise the list fields during qpd_decode_list (mask: the list call's).
+template <class Plan>
+void list_at(const qpd_decoder *d, const uint8_t *out, Plan &P) {
+    const qpd_list::Req &rq = d->ls_req;
+    if (!rq.any()) {
+        P.ls_bits = nullptr;
+        P.ls_metric = nullptr;
+        P.ls_pass = nullptr;
+        P.ls_chosen = nullptr;
+        return;
+    }
+    const int64_t f0 = (out - d->st_out0) / d->out_bits;
+    P.crc_mask = rq.mask;
+    P.ls_bits = rq.bits + f0 * d->L * d->K;
+    P.ls_metric = rq.metric ? rq.metric + f0 * d->L : nullptr;
+    P.ls_pass = rq.pass ? rq.pass + f0 * d->L : nullptr;
+    P.ls_chosen = rq.chosen ? rq.chosen + f0 : nullptr;
+}
+
 // dmetric (qpd_dmetric, a float FastSC decoder): the launch runs the kernel's DM twin, which writes
 // the frames' blind-detection metrics there and takes a NULL out; the plain kernels do not read it.
 template <class In>
 int launch_generic(qpd_decoder *d, const In *in, int64_t B, uint8_t *out, int grid, hipStream_t st,
                    double *dmetric = nullptr) {
-    const void *kfn = dmetric ? qpd::dmetric_kernel() : generic_kernel(d->kind, d->dom, d->L > qpd::kMaxL);
+    const void *kfn = dmetric            ? qpd::dmetric_kernel()
+                      : d->ls_req.any() ? qpd::generic_list_kernel(d->kind, d->dom, d->L > qpd::kMaxL)
+                                        : generic_kernel(d->kind, d->dom, d->L > qpd::kMaxL);
     if (!kfn) return fail(QPD_E_INVALID, "bad kind");
     qpd::DevPlan P = d->plan;
     P.task_base = d->task_base;
     status_at(d, out, P);
+    list_at(d, out, P);
     const In *in_arg = in;
     void *args[] = {&P, &in_arg, &B, &out, &dmetric};
     const int rc = timed_launch(d, QPD_KC_DECODE, st, [&]() -> int {
@@ -92,12 +114,14 @@ int fast_launch(qpd_decoder *d, qpd::FastPlan fp, const int32_t *in, int64_t Bc,
     const int sets = prefix ? d->pfx_sets : d->sets;
     const int64_t tw = (int64_t)fp.fpw * sets;  // frames per wave task
     // a status call's decode launch runs the plan's ST twin (the plain kernels do not read the status fields)
-    const bool status = !prefix && d->st_req.any();
+    // ... and a list call's the LIST twin
+    const bool status = !prefix && d->st_req.any(), list = !prefix && d->ls_req.any();
     const void *kfn = prefix ? prefix_kernel(d->kind, sets, d->pw1)
-                             : fast_kernel(d->kind, d->sets, d->l8, d->r1l, d->pw1, d->w16, status);
+                             : fast_kernel(d->kind, d->sets, d->l8, d->r1l, d->pw1, d->w16, list ? 2 : status ? 1 : 0);
     if (!kfn) return fail(QPD_E_INVALID, "bad kind");
     qpd::FastStatus so{};
     if (status) status_at(d, out, so);
+    if (list) list_at(d, out, so);
     const int64_t fgroups = (Bc + tw - 1) / tw;
     int fgrid = (int)std::min<int64_t>(fgroups, d->max_waves);
     if (!QPD_DYN) {
@@ -285,6 +309,19 @@ struct StatusScope {
     }
     ~StatusScope() {
         d->st_req = qpd_stat::Req();
+        d->st_out0 = nullptr;
+    }
+};
+
+// The list request of a call, likewise.
+struct ListScope {
+    qpd_decoder *d;
+    ListScope(qpd_decoder *d_, const qpd_list::Req &rq, const uint8_t *out0) : d(d_) {
+        d->ls_req = rq;
+        d->st_out0 = out0;
+    }
+    ~ListScope() {
+        d->ls_req = qpd_list::Req();
         d->st_out0 = nullptr;
     }
 };

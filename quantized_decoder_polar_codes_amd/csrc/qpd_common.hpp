@@ -229,11 +229,12 @@ __device__ __forceinline__ int stable_rank(double pm, int gl, int gbase, int L) 
 // `rank` = this path's position in the argsort(PML) order.  `crc_mask`: XORed
 // onto the low bits of the register before the compare (qpd_status_args.crc_mask,
 // CASCLWithRNTI.cpp:222-224; 0: none).  *passed: a path passed the compare -- the
-// output path is the first that did (the reference's isPass).
+// output path is the first that did (the reference's isPass).  own (list output,
+// else NULL): this lane's own compare.
 template <class WordFn>
 __device__ __forceinline__ int ca_winner_ranked(int rank, int gl, int gbase, int L, int N, const uint32_t *info_mask,
                                                 int A, int chk, int crc_n, uint32_t crc_q, WordFn word,
-                                                uint32_t crc_mask, bool *passed) {
+                                                uint32_t crc_mask, bool *passed, bool *own = nullptr) {
     const int K = A + chk;
     const uint32_t top = 1u << (crc_n - 1);
     const uint32_t mask = (top << 1) - 1u;  // crc_n = 32: 0 - 1 = all ones
@@ -268,6 +269,7 @@ __device__ __forceinline__ int ca_winner_ranked(int rank, int gl, int gbase, int
         }
     }
     *passed = bk < kMaxLWide;
+    if (own) *own = pass;
     return best;
 }
 

@@ -19,6 +19,7 @@
 #include "qpd_chunk.hpp"
 #include "qpd_host.hpp"
 #include "qpd_status.hpp"
+#include "qpd_list.hpp"
 
 namespace {
 
@@ -165,6 +166,12 @@ struct qpd_decoder {
     // first frame from its own `out` (status_at, qpd_capi_decode.hpp).
     qpd_stat::Req st_req;
     const uint8_t *st_out0 = nullptr;
+    // qpd_decode_list, likewise (st_out0: the call's d_out, or ls_out when it gave none)
+    qpd_list::Req ls_req;
+    DeviceBuf ls_out;  // the bits of a qpd_decode_list call without d_out
+    size_t ls_out_bytes = 0;
+    DeviceBuf h_ls;  // qpd_decode_list_host's device outputs: bits, metrics, flags, chosen
+    size_t h_ls_bytes = 0;
     // qpd_profile: HIP events around every launch, per kernel class
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[QPD_KC_COUNT];

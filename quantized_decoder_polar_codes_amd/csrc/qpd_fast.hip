@@ -30,13 +30,23 @@
 #include "qpd_fast_bot.hpp"
 #include "qpd_fast_special.hpp"
 
+// The tail's mode (lut_fast_kernel's ST): the bits alone, + the decode status
+// (qpd_decode_status), + the whole list (qpd_decode_list).
+#define QPD_TAIL_PLAIN 0
+#define QPD_TAIL_ST 1
+#define QPD_TAIL_LIST 2
+
 // A unit compiled with QPD_STATUS_UNIT (the *_st.hip wrappers) instantiates the ST
-// kernels and names its lookup function <name>_st.
-#ifdef QPD_STATUS_UNIT
-#define QPD_ST true
+// kernels and names its lookup function <name>_st; with QPD_LIST_UNIT (the *_ls.hip
+// wrappers) the LIST kernels, <name>_ls.
+#if defined(QPD_LIST_UNIT)
+#define QPD_ST QPD_TAIL_LIST
+#define QPD_UNIT_FN(f) f##_ls
+#elif defined(QPD_STATUS_UNIT)
+#define QPD_ST QPD_TAIL_ST
 #define QPD_UNIT_FN(f) f##_st
 #else
-#define QPD_ST false
+#define QPD_ST QPD_TAIL_PLAIN
 #define QPD_UNIT_FN(f) f
 #endif
 
@@ -61,8 +71,10 @@ namespace qpd {
 // ST: the tail also writes the decode status (qpd_decode_status: the output path's
 // metric and CRC verdict, the CRC mask) -- instantiations of their own (the *_st.hip
 // units), so that the plain decode kernels compile to what they are without it.
+// ST = QPD_TAIL_LIST (the *_ls.hip units): the tail writes every path of the list
+// instead (qpd_decode_list, the LIST block below).
 template <int KIND, int NS, bool L8, bool R1L = false, bool PFX = false, bool PW1 = false, bool W16 = false,
-          bool ST = false>
+          int ST = QPD_TAIL_PLAIN>
 __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
                                 : W16 ? QPD_WPE_W16
                                 : NS == 2 ? (KIND == K_SCL_LUT && !PFX ? QPD_WPE2_SCL : KIND == K_FASTSCL_LUT ? QPD_WPE2_FSCL : QPD_WPE2)
@@ -468,7 +480,8 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
         // the frame's gs lanes (wpl words each; the cross-lane butterfly stages
         // by shuffles) and staged in this set's LDS rows for the output gather.
         const int wpl = nwr / gs;
-        const bool split = kList && P.crc_n == 0 && nwr >= gs && wpl <= 8 && wpl <= P.lds_rows;
+        constexpr bool LS = ST == QPD_TAIL_LIST;  // every path's row is output: no split
+        const bool split = !LS && kList && P.crc_n == 0 && nwr >= gs && wpl <= 8 && wpl <= P.lds_rows;
         if (!split) {  // every path re-encodes its own row (CRC-aided: each path's CRC is checked)
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
@@ -488,6 +501,65 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const Mem &M = Mv[s];
+            if constexpr (LS) {
+                // The list (qpd_decode_list): lane gl is list slot gl, its rank the path's
+                // position in argsort(PML) (stable, L <= 16); candidate r = the lane of rank
+                // r, whose K decisions the frame's gs lanes gather together (the output
+                // gather below with that lane as its source), r = 0 .. L-1.  Each lane
+                // writes its own metric and CRC verdict at its rank.
+                const int rank = stable_rank(stv[s].pm, gl, gbase, L);
+                bool passed = false, own = false;
+                int best = 0;
+                if (P.crc_n > 0)
+                    best = ca_winner_ranked(rank, gl, gbase, L, N, P.info_mask, P.ca_A, P.K - P.ca_A, P.crc_n, P.crc_q,
+                                            [&](int w) { return M.ld(rl, r0 + w, lane); }, SO.crc_mask, &passed, &own);
+                const int64_t frame = (task * NS + s) * fpw + lane / gs;
+                const bool live = frame < B;
+                auto bit = [&](int pos, int src) { return (M.ldv(rl, r0 + (pos >> 5), src) >> (pos & 31)) & 1u; };
+                // nb decisions of the path in lane src -> dst, by the frame's lanes
+                auto gather = [&](uint8_t *dst, int nb, int src, bool dw) {
+                    if (dw) {  // four bytes per store; 4 stores' loads issued together
+                        uint32_t *o32 = (uint32_t *)dst;
+                        const int nc = nb >> 2;
+                        for (int c0 = gl; c0 < nc; c0 += 4 * gs) {
+                            uint32_t wv[4];
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                const int c = c0 + k * gs;
+                                wv[k] = 0;
+                                if (c < nc) {
+                                    const int4 pp = *(const int4 *)(P.info_pos + 4 * c);
+                                    wv[k] = bit(pp.x, src) | (bit(pp.y, src) << 8) | (bit(pp.z, src) << 16) |
+                                            (bit(pp.w, src) << 24);
+                                }
+                            }
+#pragma unroll
+                            for (int k = 0; k < 4; ++k)
+                                if (c0 + k * gs < nc) o32[c0 + k * gs] = wv[k];
+                        }
+                    } else {
+                        for (int t = gl; t < nb; t += gs) dst[t] = (uint8_t)bit(P.info_pos[t], src);
+                    }
+                };
+                const bool dword_ls = (P.K & 3) == 0 && ((uintptr_t)SO.ls_bits & 3) == 0;
+                for (int r = 0; r < L; ++r) {
+                    // the group's lane of rank r (one per group; the ballot by the whole wave)
+                    const uint64_t m = __ballot(gl < L && rank == r) >> gbase;
+                    const int src = gbase + (__builtin_ctzll(m | (1ull << 63)) & (gs - 1));
+                    if (r == 0 && P.crc_n == 0) best = src - gbase;  // the first minimum (H6)
+                    if (live) gather(SO.ls_bits + (frame * L + r) * (int64_t)P.K, P.K, src, dword_ls);
+                }
+                const int crank = lane_read(rank, gbase + best);
+                if (live) {
+                    if (gl < L) {
+                        if (SO.ls_metric) SO.ls_metric[frame * L + rank] = stv[s].pm;
+                        if (SO.ls_pass) SO.ls_pass[frame * L + rank] = (uint8_t)own;
+                    }
+                    if (gl == 0 && SO.ls_chosen) SO.ls_chosen[frame] = crank;
+                    if (out) gather(out + frame * P.out_k, P.out_k, gbase + best, dword_out);
+                }
+                continue;
+            }
             int best = 0;
             bool passed = false;
             if (kList && P.crc_n > 0) {

@@ -57,6 +57,13 @@ struct FastStatus {
     uint32_t crc_mask;   // XORed onto the CRC register's low bits before the compare (ca_winner)
     double *st_metric;   // [B] path metric of the output path, or NULL
     uint8_t *st_pass;    // [B] 1 = the output path passed the CRC, or NULL
+    // List output (qpd_decode_list), read by the LIST instantiations' tail alone: the
+    // candidates from the launch's first frame on, in argsort(PML) order.  After the
+    // status fields: the last argument's tail, so that no other offset moves.
+    uint8_t *ls_bits;    // [B][L][K] every path's decisions at the information positions
+    double *ls_metric;   // [B][L] or NULL
+    uint8_t *ls_pass;    // [B][L] or NULL: the path's own CRC compare
+    int32_t *ls_chosen;  // [B] or NULL: the candidate whose bits `out` receives
 };
 
 // Row access in either space.  `in_lds` is wave-uniform.  The global slab is

@@ -79,6 +79,12 @@ struct DevPlan {
     uint32_t crc_mask;   // XORed onto the CRC register's low bits before the compare (ca_winner)
     double *st_metric;   // [B] path metric of the output path, or NULL
     uint8_t *st_pass;    // [B] 1 = the output path passed the CRC, or NULL
+    // List output (qpd_decode_list), per launch, read by the LS instantiations alone: the candidates
+    // from the launch's first frame on, in argsort(PML) order (L <= 16: stable).
+    uint8_t *ls_bits;    // [B][L][K] every path's decisions at the information positions
+    double *ls_metric;   // [B][L] or NULL
+    uint8_t *ls_pass;    // [B][L] or NULL: the path's own CRC compare
+    int32_t *ls_chosen;  // [B] or NULL: the candidate whose bits `out` receives
 };
 
 __device__ __forceinline__ double vcl_at(const DevPlan &P, int row, int pos, int sym) {
@@ -357,14 +363,17 @@ __device__ __forceinline__ double pow2_rcp(int k) { return __longlong_as_double(
 // |sum| / temp at every REP node (:91-97), added in traversal order -- written
 // to dmetric[frame]; out may then be NULL (no re-encode, no bits).  The plain
 // instantiations never read dmetric.
+// LS (list kinds, qpd_k_generic_ls.hip): the tail writes every path of the list
+// (qpd_decode_list) -- a twin too, so that the plain instantiations never hold it.
 // ---------------------------------------------------------------------------
-template <int KIND, int DOM, int ML, bool DM = false>
+template <int KIND, int DOM, int ML, bool DM = false, bool LS = false>
 __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
                                                             const std::conditional_t<DOM == DOM_LUT, int32_t, double>
                                                                 *__restrict__ in,
                                                             int64_t B, uint8_t *__restrict__ out,
                                                             double *__restrict__ dmetric) {
     static_assert(!DM || (KIND == K_FASTSC_LUT && DOM == DOM_FLOAT), "the D-metric is float FastSC's");
+    static_assert(!LS || KIND == K_SCL_LUT || KIND == K_FASTSCL_LUT, "list output: the list kinds");
     constexpr bool kList = (KIND == K_SCL_LUT || KIND == K_FASTSCL_LUT);
     constexpr bool kLut = DOM == DOM_LUT;
     using In = std::conditional_t<kLut, int32_t, double>;
@@ -734,6 +743,49 @@ __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
                     *a ^= row_ptr(wsc, P.Ro + i + mw + j)[lane];
                 }
         wave_sync();
+        if constexpr (LS) {
+            {  // the whole list (qpd_decode_list), L <= 16
+                // lane gl is list slot gl and holds its re-encoded row: candidate r = the
+                // lane of rank r in the stable argsort(PML) order, its K decisions gathered
+                // by the frame's gs lanes; each lane writes its own metric and CRC verdict
+                // at its rank; the output path is the first that passed, else candidate 0
+                check_keys<DOM>(P, pm, pm);  // the metrics are sorted
+                const int rank = stable_rank(pm, gl, gbase, L);
+                bool passed = false, own = false;
+                int best = 0;
+                if (P.crc_n > 0)
+                    best = ca_winner_ranked(rank, gl, gbase, L, P.N, P.info_mask, P.ca_A, P.ca_chk, P.crc_n, P.crc_q,
+                                            [&](int w) { return row_ptr(wsc, P.Ro + w)[lane]; }, P.crc_mask, &passed, &own);
+                const uint32_t *rb = row_ptr(wsc, P.Ro);
+                for (int r = 0; r < L; ++r) {
+                    const uint64_t m = __ballot(gl < L && rank == r) >> gbase;  // (by the whole wave)
+                    const int src = gbase + (__builtin_ctzll(m | (1ull << 63)) & (gs - 1));
+                    if (r == 0 && P.crc_n == 0) best = src - gbase;  // the first minimum (H6)
+                    if (frame_ok) {
+                        uint8_t *dst = P.ls_bits + (frame * L + r) * (int64_t)P.K;
+                        for (int t = gl; t < P.K; t += gs) {
+                            const int pos = P.info_pos[t];
+                            dst[t] = (uint8_t)((rb[(size_t)(pos >> 5) * 64 + src] >> (pos & 31)) & 1u);
+                        }
+                    }
+                }
+                const int crank = __shfl(rank, gbase + best);
+                if (frame_ok) {
+                    if (gl < L) {
+                        if (P.ls_metric) P.ls_metric[frame * L + rank] = pm;
+                        if (P.ls_pass) P.ls_pass[frame * L + rank] = (uint8_t)own;
+                    }
+                    if (gl == 0 && P.ls_chosen) P.ls_chosen[frame] = crank;
+                    if (out)
+                        for (int t = gl; t < P.out_k; t += gs) {
+                            const int pos = P.info_pos[t];
+                            out[frame * P.out_k + t] = (uint8_t)((rb[(size_t)(pos >> 5) * 64 + gbase + best] >> (pos & 31)) & 1u);
+                        }
+                }
+                wave_sync();
+                continue;
+            }
+        }
         // best path: first minimum of the path metrics (H6, SCLLUTDecoder.cpp:244)
         int best = 0;
         bool passed = false;

@@ -216,6 +216,16 @@ class Engine {
     bool want_dmetric = false;
     double last_dmetric = 0.0;
 
+    // List output (qpd_decode_list_host): while list.bits is set, a decode stores all
+    // L paths of the frame there in argsort(PML) order (finish_list) and a NULL `out`
+    // is allowed.  The pointers are the frame's own: [L][K], [L], [L], [1].
+    struct ListOut {
+        uint8_t *bits = nullptr;
+        double *metric = nullptr;
+        uint8_t *pass = nullptr;
+        int32_t *chosen = nullptr;
+    } list;
+
     // One frame: y[N] (int32 symbols or float64 LLRs) -> out[out_k].
     // Returns 0, or qpd::ERR_SYMBOL for a channel symbol outside [0, v).
     template <class In>
@@ -239,7 +249,10 @@ class Engine {
         else
             run<true>();
         if (flags) return flags;  // NaN metric: the reference's sort is undefined there, stop
-        if (out || !want_dmetric) finish(out);
+        if (list.bits)
+            finish_list(out);
+        else if (out || !want_dmetric)
+            finish(out);
         return flags;
     }
 
@@ -676,6 +689,47 @@ class Engine {
         last_metric = pm[best];
         const uint64_t *x = reencode(best);
         for (int t = 0; t < P.out_k; ++t) out[t] = bit(x, P.info_pos[t]);
+    }
+
+    // The list run (L <= 16: the argsort is the stable insertion sort, so candidate 0 is
+    // also the first minimum the kinds without CRC output): every path in argsort(PML)
+    // order with its K decisions, its metric and -- the CA epilogue above without its
+    // early break -- its own CRC compare; the output path is the first that passed, else
+    // candidate 0.
+    void finish_list(uint8_t *out) {
+        const int L = P.L, K = P.K;
+        last_pass = false;
+        if (nan_key(pm.data(), L)) return;
+        std_sort_index(idx.data(), pm.data(), L);
+        int chosen = 0;
+        const uint32_t top = P.crc_n > 0 ? 1u << (P.crc_n - 1) : 0u, mask = (top << 1) - 1u;
+        for (int r = 0; r < L; ++r) {
+            const uint64_t *x = reencode(idx[r]);
+            uint8_t *b = list.bits + (size_t)r * K;
+            for (int t = 0; t < K; ++t) b[t] = bit(x, P.info_pos[t]);
+            if (list.metric) list.metric[r] = pm[idx[r]];
+            if (P.crc_n > 0) {
+                uint32_t reg = 0;
+                bool pass = true;
+                for (int t = 0; t < P.ca_A + P.ca_chk; ++t) {
+                    const uint32_t bt = b[t];
+                    if (t < P.ca_A) {
+                        const uint32_t fb = bt ^ ((reg & top) ? 1u : 0u);
+                        reg = ((reg << 1) & mask) ^ (P.crc_q & (0u - fb));
+                    } else {
+                        pass = pass && bt == (((reg ^ crc_mask) >> (P.crc_n - 1 - (t - P.ca_A))) & 1u);
+                    }
+                }
+                if (list.pass) list.pass[r] = (uint8_t)pass;
+                if (pass && !last_pass) {
+                    chosen = r;
+                    last_pass = true;
+                }
+            }
+        }
+        if (list.chosen) *list.chosen = chosen;
+        last_metric = pm[idx[chosen]];
+        if (out) std::memcpy(out, list.bits + (size_t)chosen * K, P.out_k);
     }
 };
 

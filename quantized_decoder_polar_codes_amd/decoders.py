@@ -32,7 +32,7 @@ from . import _lib
 from .lut import PackedLUT, pack_luts
 from .quant import LloydQuant, UniformQuant, pack_lloyd, pack_uniform
 
-__all__ = ["ChannelQuantizer", "DecodeStatus", "SCDecoder", "SCLUTDecoder", "SCLLUTDecoder", "FastSCLUTDecoder", "FastSCLLUTDecoder",
+__all__ = ["ChannelQuantizer", "DecodeStatus", "DecodeList", "SCDecoder", "SCLUTDecoder", "SCLLUTDecoder", "FastSCLUTDecoder", "FastSCLLUTDecoder",
            "CASCLLUTDecoder", "CAFastSCLLUTDecoder", "SCLDecoder", "CASCLDecoder", "FastSCDecoder", "FastSCLDecoder",
            "SCUniformQuantizedDecoder", "SCLUniformQuantizedDecoder", "SCLloydQuantizedDecoder",
            "SCLLloydQuantizedDecoder"]
@@ -59,6 +59,20 @@ class DecodeStatus(NamedTuple):
 
     metric: object
     crc_pass: object
+
+
+class DecodeList(NamedTuple):
+    """What ``decode_list_batch`` returns: all L candidates of every frame in the reference's
+    argsort order of the path metrics (qpd_decode_list, include/qpd.h) -- ``bits`` (uint8
+    [B, L, K]), ``metric`` (float64 [B, L]), ``crc_pass`` (bool [B, L]; None for a decoder
+    without CRC), ``chosen`` (int32 [B]: the candidate whose bits are output) and ``out`` (uint8
+    [B, out_bits], ``decode_batch``'s bits).  numpy arrays or torch CUDA tensors."""
+
+    bits: object
+    metric: object
+    crc_pass: object
+    chosen: object
+    out: object
 
 
 def _torch():
@@ -273,6 +287,60 @@ class _DecoderBase:
         ty = _lib.QPD_IN_F64 if self._float_input else _lib.QPD_IN_U8 if u8 else _lib.QPD_IN_I32
         _lib.check(lib.qpd_decode_status_host(self._h, _ptr(a), ty, B, _ptr(out), ctypes.byref(sa)))
         return out, DecodeStatus(metric, None if flag is None else flag.astype(bool))
+
+    def decode_list_batch(self, x, crc_mask=None):
+        """All L candidates of a list decode (qpd_decode_list / _host) -> :class:`DecodeList`:
+        ``bits [B, L, K]`` (for the CRC-aided decoders message and CRC tail), ``metric [B, L]``,
+        ``crc_pass [B, L]`` (None without CRC), ``chosen [B]`` and ``out [B, out_bits]``, the
+        bits of ``decode_batch``.  Candidate r is the path at position r of the reference's
+        argsort of the path metrics (ascending, ties by list slot); ``chosen`` is the r whose
+        bits ``out`` holds.  ``crc_mask`` as for ``decode_batch(return_status=True)``.  numpy in
+        -> numpy out (synchronous); a torch CUDA tensor is read where it lies, on the current
+        stream -> torch CUDA tensors.  List decoders with 2 <= L <= 16."""
+        torch = _torch()
+        lib = _lib.load()
+        mask = None
+        la = _lib.QpdListArgs()
+        if crc_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(crc_mask).reshape(-1).astype(np.uint8))
+            la.crc_mask, la.crc_mask_bits = _ptr(mask), mask.size
+        ca, L, K = self._crc_aided, int(self.L), int(self.K)
+        if torch is not None and isinstance(x, torch.Tensor) and x.is_cuda:
+            u8 = not self._float_input and x.dtype == torch.uint8
+            want = torch.float64 if self._float_input else torch.uint8 if u8 else torch.int32
+            xs = x.reshape(-1, self.N).to(want).contiguous()
+            B = xs.shape[0]
+            dev = xs.device
+            out = torch.empty((B, self.out_bits), dtype=torch.uint8, device=dev)
+            bits = torch.empty((B, L, K), dtype=torch.uint8, device=dev)
+            metric = torch.empty((B, L), dtype=torch.float64, device=dev)
+            flag = torch.empty((B, L), dtype=torch.uint8, device=dev) if ca else None
+            chosen = torch.empty(B, dtype=torch.int32, device=dev)
+            la.cand_bits = ctypes.c_void_p(bits.data_ptr())
+            la.cand_metric = ctypes.c_void_p(metric.data_ptr())
+            la.cand_pass = None if flag is None else ctypes.c_void_p(flag.data_ptr())
+            la.chosen = ctypes.c_void_p(chosen.data_ptr())
+            ty = _lib.QPD_IN_F64 if self._float_input else _lib.QPD_IN_U8 if u8 else _lib.QPD_IN_I32
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.qpd_decode_list(self._h, ctypes.c_void_p(xs.data_ptr()), ty, B,
+                                           ctypes.c_void_p(out.data_ptr()), ctypes.byref(la), ctypes.c_void_p(stream)))
+            return DecodeList(bits, metric, None if flag is None else flag.bool(), chosen, out)
+        if torch is not None and isinstance(x, torch.Tensor):
+            x = x.numpy()
+        a = np.asarray(x)
+        u8 = not self._float_input and a.dtype == np.uint8
+        want = np.float64 if self._float_input else np.uint8 if u8 else np.int32
+        a = np.ascontiguousarray(a.astype(want, copy=False).reshape(-1, self.N))
+        B = a.shape[0]
+        out = np.zeros((B, self.out_bits), dtype=np.uint8)
+        bits = np.zeros((B, L, K), dtype=np.uint8)
+        metric = np.zeros((B, L), dtype=np.float64)
+        flag = np.zeros((B, L), dtype=np.uint8) if ca else None
+        chosen = np.zeros(B, dtype=np.int32)
+        la.cand_bits, la.cand_metric, la.cand_pass, la.chosen = _ptr(bits), _ptr(metric), _ptr(flag), _ptr(chosen)
+        ty = _lib.QPD_IN_F64 if self._float_input else _lib.QPD_IN_U8 if u8 else _lib.QPD_IN_I32
+        _lib.check(lib.qpd_decode_list_host(self._h, _ptr(a), ty, B, _ptr(out), ctypes.byref(la)))
+        return DecodeList(bits, metric, None if flag is None else flag.astype(bool), chosen, out)
 
     def decode_batch(self, x, return_status: bool = False, crc_mask=None):
         """Decode B frames.  numpy [B, N] -> numpy uint8 [B, K] (synchronous);
