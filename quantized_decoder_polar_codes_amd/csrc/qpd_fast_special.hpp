@@ -28,7 +28,11 @@ __device__ __forceinline__ uint32_t hibit(uint32_t x) { return 31u - (uint32_t)_
 // swapped-in entry stops the scan there), the right stops likewise, and only
 // the swaps touch LDS.  Returns `end` (partition_prefix); heap-sort fallbacks
 // (the depth limit, never on the bench code) run stl::heap_sort as the
-// reference does.
+// reference does -- one lane's serial sort inside the ballot loop while the
+// others go on partitioning.  tests/test_gpu_r1_nodes.py runs that branch on
+// the device (tests/native/r1_harness.hip: the witnesses of
+// tests/golden/r1_heap_witnesses.json in lanes beside arrays that partition to
+// a natural end).
 template <class Seq>
 __device__ __forceinline__ int partition_prefix_masked(Seq &s, int temp, int m) {
     int f = 0, l = temp, dl = 0, end = temp;
