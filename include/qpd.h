@@ -363,7 +363,8 @@ int qpd_dmetric_host(qpd_decoder *dec, const double *h_llr, int64_t B, double *h
  * check saw a channel symbol outside [0, v), a Lloyd bisect index outside
  * the reconstruction list, or a NaN path metric reaching a list selection
  * (each undefined behaviour in the reference), or a NaN LLR in qpd_quantize_llr /
- * qpd_decode_llr; waits for the decoder's previous work (not the whole device). */
+ * qpd_decode_llr, or a message byte other than 0 / 1 in qpd_encode / qpd_tx_frames;
+ * waits for the decoder's previous work (not the whole device). */
 int qpd_check_input_error(qpd_decoder *dec);
 
 /*
@@ -431,6 +432,73 @@ int qpd_mc_llr(qpd_decoder *dec, const qpd_mc_channel *ch, const double *rec, ui
  * generated, then decoded, then the counters over the whole range. */
 int qpd_mc_decode_f64(qpd_decoder *dec, const qpd_mc_channel *ch, const double *rec, uint64_t seed, int64_t frame0,
                       int64_t B, uint8_t *d_msg, uint8_t *d_out, int64_t *d_counts, void *stream);
+
+/*
+ * The transmit side for messages the caller chooses.  Replaces the package every
+ * reference driver imports and the reference does not ship,
+ *     PolarBDEnc.Encoder.PolarEnc   PolarEnc(N, K, frozenbits, msgbits).encode(msg)
+ *     PolarBDEnc.Encoder.CRCEnc     CRCEnc(crc_n, crc_p).encode(msg)
+ *         mainQuantizedDecoder_LLRDomain.py:10-11, :72-73, :153-158; mainFPDecoder.py:12-13
+ * (the CRC is CRC::encoding, utils.cpp:77-92, over the handle's taps), batched, and
+ * the drivers' channel behind it (mainQuantizedDecoder_LLRDomain.py:161-176) for such
+ * messages: qpd_mc_frames / qpd_mc_llr with the message given instead of drawn.
+ *
+ * dec: any decoder kind -- its code (N, K, frozen_bits) and, for the CRC-aided
+ * kinds, its A, crc_n and taps are what counts.  msg: uint8 [B][A] for the CRC-aided
+ * kinds, [B][K] otherwise, entries 0 / 1.  The information bits are the message, for
+ * the CRC-aided kinds followed by the first K - A bits of its check code; u[information
+ * positions] = information bits, frozen positions 0, codeword x = u F^{(x)n} in natural
+ * order, one byte per bit.
+ * qpd_tx_args (may be NULL: no mask, signal present):
+ *   crc_mask / crc_mask_bits  a mask for the check code (e.g. an RNTI), placed as in
+ *       qpd_status_args: mask bit l is XORed onto check-code bit crc_n - crc_mask_bits
+ *       + l, before the check code is cut to its first K - A bits -- the mirror of
+ *       qpd_decode_status's compare, so a word encoded under a mask and decoded
+ *       noiselessly under the same mask passes.  One mask per call.  QPD_E_INVALID on a
+ *       kind without CRC, for crc_mask_bits outside [0, crc_n], a NULL mask with
+ *       bits > 0, or an entry above 1.
+ *   no_signal  qpd_tx_frames only (QPD_E_INVALID in qpd_encode*): 1 = y = sigma *
+ *       noise, the BPSK term dropped and nothing else -- a candidate nothing was sent
+ *       in.  The outputs then do not depend on d_msg, which may be NULL.
+ * A CRC-aided code with K - A > crc_n (QPD_CASCL_FLOAT with A + crc_n < K) has no check
+ * bits to fill its message with: QPD_E_UNSUPPORTED, as in qpd_mc_llr.
+ * A message byte other than 0 / 1 is undefined in the reference; here it counts as its
+ * low bit and raises the decoder's input-error word (qpd_check_input_error; the host
+ * variant returns QPD_E_INPUT, its outputs written); the other frames are unaffected.
+ *
+ * qpd_encode: device pointers; d_info ([B][K]) and d_codeword ([B][N]) may each be
+ * NULL, both NULL is QPD_E_INVALID.  qpd_encode_host: the same from host buffers,
+ * always on the host (the same word-packed algorithm; no crossover to the device).
+ *
+ * qpd_tx_frames: the received frames of global frame ids [frame0, frame0 + B) for
+ * d_msg ([B] rows), d_frames [B][N] by out_type: int32 symbols, uint8 symbols (the
+ * int32 symbol narrowed; q <= 256, QPD_E_INVALID otherwise) or float64 LLRs.  The
+ * noise of (seed, frame id, position) is qpd_mc_frames' noise -- the same Philox
+ * counter and arithmetic, quantizer and rec rule: when d_msg holds the messages
+ * qpd_mc_frames wrote for the range, d_frames is that call's symbols, or qpd_mc_llr's
+ * doubles, bit for bit.  ch as for qpd_mc_frames (symbols) / qpd_mc_llr (LLRs); rec
+ * applies to QPD_TX_LLR_F64 only (QPD_E_INVALID with the symbol outputs).
+ *
+ * Any base address for d_msg, d_info, d_codeword and uint8 d_frames: rows that are a
+ * multiple of 8 bytes on an 8-byte aligned base are moved 8 bytes at a time (uint8
+ * symbols: 2 on an even base), everything else byte by byte.  int32 / float64
+ * d_frames need their type's alignment (QPD_E_INVALID otherwise; 8 / 16 bytes are the
+ * fast cases).  Frames >= B and bytes past the last row are never written.  All
+ * refusals return before any launch, qpd_last_error naming the argument.  Stream
+ * ordering and the per-handle lock as for qpd_mc_frames.
+ */
+typedef struct qpd_tx_args {
+    const uint8_t *crc_mask;   /* host, [crc_mask_bits] of 0/1, or NULL; placed as in qpd_status_args */
+    int32_t crc_mask_bits;     /* 0..crc_n */
+    int32_t no_signal;         /* qpd_tx_frames only: 1 = y = sigma * noise (no BPSK term): an empty candidate */
+} qpd_tx_args;
+int qpd_encode(qpd_decoder *dec, const uint8_t *d_msg, int64_t B, const qpd_tx_args *tx, uint8_t *d_info,
+               uint8_t *d_codeword, void *stream);
+int qpd_encode_host(qpd_decoder *dec, const uint8_t *h_msg, int64_t B, const qpd_tx_args *tx, uint8_t *h_info,
+                    uint8_t *h_codeword);
+enum qpd_tx_out { QPD_TX_SYM_I32 = 0, QPD_TX_SYM_U8 = 1, QPD_TX_LLR_F64 = 2 };
+int qpd_tx_frames(qpd_decoder *dec, const qpd_mc_channel *ch, const double *rec, uint64_t seed, int64_t frame0,
+                  int64_t B, const uint8_t *d_msg, const qpd_tx_args *tx, int32_t out_type, void *d_frames, void *stream);
 
 /*
  * LLRs on the LUT decoders: the driver's channel quantizer

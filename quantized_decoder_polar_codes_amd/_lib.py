@@ -55,6 +55,9 @@ EXPORTED = (
     "qpd_decode_list_host",
     "qpd_dmetric",
     "qpd_dmetric_host",
+    "qpd_encode",
+    "qpd_encode_host",
+    "qpd_tx_frames",
 )
 QPD_KC_PRE, QPD_KC_DECODE, QPD_KC_MC, QPD_KC_PFX, QPD_KC_COUNT = range(5)
 QPD_PROBE_BPERMUTE, QPD_PROBE_READ_B32, QPD_PROBE_READ_B64 = range(3)
@@ -62,6 +65,7 @@ QPD_HOST_AUTO, QPD_HOST_GPU, QPD_HOST_CPU = range(3)
 QPD_RAN_NONE, QPD_RAN_GPU, QPD_RAN_HOST = range(3)
 QPD_LLR_F64, QPD_LLR_F32 = range(2)
 QPD_IN_I32, QPD_IN_U8, QPD_IN_F64 = range(3)
+QPD_TX_SYM_I32, QPD_TX_SYM_U8, QPD_TX_LLR_F64 = range(3)
 
 _P = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -134,6 +138,14 @@ class QpdListArgs(ctypes.Structure):
         ("cand_metric", _P),
         ("cand_pass", _P),
         ("chosen", _P),
+    ]
+
+
+class QpdTxArgs(ctypes.Structure):
+    _fields_ = [
+        ("crc_mask", _P),
+        ("crc_mask_bits", _i32),
+        ("no_signal", _i32),
     ]
 
 
@@ -253,6 +265,14 @@ def load():
         L.qpd_dmetric.restype = ctypes.c_int
         L.qpd_dmetric_host.argtypes = [_P, _P, _i64, _P, _P]
         L.qpd_dmetric_host.restype = ctypes.c_int
+    if not os.environ.get("QPD_LIB") or hasattr(L, "qpd_encode"):
+        L.qpd_encode.argtypes = [_P, _P, _i64, ctypes.POINTER(QpdTxArgs), _P, _P, _P]
+        L.qpd_encode.restype = ctypes.c_int
+        L.qpd_encode_host.argtypes = [_P, _P, _i64, ctypes.POINTER(QpdTxArgs), _P, _P]
+        L.qpd_encode_host.restype = ctypes.c_int
+        L.qpd_tx_frames.argtypes = [_P, ctypes.POINTER(QpdMcChannel), _P, ctypes.c_uint64, _i64, _i64, _P,
+                                    ctypes.POINTER(QpdTxArgs), _i32, _P, _P]
+        L.qpd_tx_frames.restype = ctypes.c_int
     if L.qpd_abi_version() != ABI_VERSION:
         raise ImportError("libqpd.so ABI version mismatch")
     L.qpd_build_id.restype = ctypes.c_char_p

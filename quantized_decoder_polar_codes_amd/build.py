@@ -47,6 +47,9 @@ UNITS = [
     ("qpd_k_generic_dm.hip", []),
     # the generic engine's list kinds with the list-output tail (qpd_decode_list)
     ("qpd_k_generic_ls.hip", []),
+    # the transmit side for caller-chosen messages (qpd_encode, qpd_tx_frames): a unit of its
+    # own, so the generator's instantiations in qpd_capi.hip's unit compile to what they were
+    ("qpd_tx.hip", []),
     ("qpd_lutgen.cpp", []),
 ]
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Werror=undef"]

@@ -3,10 +3,12 @@
 // (qpd_decoder.hpp), qpd_create's decisions (qpd_config.hpp) and steps
 // (qpd_capi_build.hpp), the device-buffer decodes (qpd_capi_decode.hpp), the
 // host-buffer ones (qpd_capi_host.hpp), the Monte-Carlo front end
-// (qpd_capi_mc.hpp), the LLR front end (qpd_capi_llr.hpp).  Host code only; this
+// (qpd_capi_mc.hpp), the LLR front end (qpd_capi_llr.hpp), the transmit side
+// (qpd_capi_tx.hpp).  Host code only; this
 // unit also compiles the small kernels (root pre-pass, widening copy,
 // Monte-Carlo, LLR quantizer, LDS probe); the decode
-// kernels are in qpd_generic.hip / qpd_fast.hip and their units.
+// kernels are in qpd_generic.hip / qpd_fast.hip and their units, the transmit
+// kernels in qpd_tx.hip.
 #include <hip/hip_runtime.h>
 
 #include "qpd.h"
@@ -24,6 +26,7 @@
 #include "qpd_capi_host.hpp"
 #include "qpd_capi_mc.hpp"
 #include "qpd_capi_llr.hpp"
+#include "qpd_capi_tx.hpp"
 
 namespace {
 
@@ -428,6 +431,52 @@ int qpd_mc_decode_f64(qpd_decoder *d, const qpd_mc_channel *ch, const double *re
     if (!run) return rc;
     hipStream_t st = (hipStream_t)stream;
     return ordered(d, st, [&]() { return mc_decode_f64(d, ch, rec, seed, frame0, B, d_msg, d_out, d_counts, st); });
+}
+
+int qpd_encode(qpd_decoder *d, const uint8_t *d_msg, int64_t B, const qpd_tx_args *tx, uint8_t *d_info, uint8_t *d_codeword,
+               void *stream) {
+    if (!d) return fail(QPD_E_INVALID, "null decoder");
+    bool run;
+    uint32_t mask;
+    std::string err;
+    const int rc = qpd_tx::check_encode(d->pub_kind, d->K, d->ca_A, d->crc_n, tx, B, d_msg, d_info, d_codeword, &mask, &run, err);
+    if (rc) return fail(rc, "qpd_encode: " + err);
+    if (!run) return QPD_OK;
+    hipStream_t st = (hipStream_t)stream;
+    return ordered(d, st, [&]() { return tx_encode_launch(d, d_msg, B, mask, d_info, d_codeword, st); });
+}
+
+int qpd_encode_host(qpd_decoder *d, const uint8_t *h_msg, int64_t B, const qpd_tx_args *tx, uint8_t *h_info,
+                    uint8_t *h_codeword) {
+    if (!d) return fail(QPD_E_INVALID, "null decoder");
+    bool run;
+    uint32_t mask;
+    std::string err;
+    int rc = qpd_tx::check_encode(d->pub_kind, d->K, d->ca_A, d->crc_n, tx, B, h_msg, h_info, h_codeword, &mask, &run, err);
+    if (rc) return fail(rc, "qpd_encode_host: " + err);
+    if (!run) return QPD_OK;
+    std::lock_guard<std::mutex> lk(d->mu);
+    if ((rc = tx_host_code(d))) return rc;
+    const int32_t flag = qpd_tx::encode_host(*d->tx_code, h_msg, B, mask, h_info, h_codeword);
+    return flag ? input_error(flag) : QPD_OK;
+}
+
+int qpd_tx_frames(qpd_decoder *d, const qpd_mc_channel *ch, const double *rec, uint64_t seed, int64_t frame0, int64_t B,
+                  const uint8_t *d_msg, const qpd_tx_args *tx, int32_t out_type, void *d_frames, void *stream) {
+    if (!d) return fail(QPD_E_INVALID, "null decoder");
+    bool run;
+    uint32_t mask;
+    std::string err;
+    int rc = qpd_tx::check_frames(d->pub_kind, d->K, d->ca_A, d->crc_n, tx, frame0, B, d_msg, out_type, ch != nullptr,
+                                  ch ? ch->q : 0, rec != nullptr, d_frames, &mask, &run, err);
+    if (rc) return fail(rc, "qpd_tx_frames: " + err);
+    if (!run) return QPD_OK;
+    if ((rc = out_type == QPD_TX_LLR_F64 ? check_llr_channel(ch, rec) : check_channel(ch))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int no_signal = tx && tx->no_signal;
+    return ordered(d, st, [&]() {
+        return tx_frames_launch(d, ch, rec, seed, frame0, B, d_msg, mask, no_signal, out_type, d_frames, st);
+    });
 }
 
 int qpd_probe_lds(int32_t device, int32_t op, double *gbps) {

@@ -14,6 +14,7 @@ int input_error(int32_t flag) {
     if (flag & qpd::ERR_LLOYD) msg += "Lloyd bisect index outside the reconstruction list (reference UB); ";
     if (flag & qpd::ERR_NAN_PM) msg += "NaN path metric reached the list sort (reference UB); ";
     if (flag & qpd::ERR_NAN_LLR) msg += "NaN LLR in decoder input (no channel symbol in the reference driver); ";
+    if (flag & qpd::ERR_MSG_BIT) msg += "message byte other than 0 or 1 in encoder input (read as its low bit); ";
     msg.resize(msg.size() - 2);
     return fail(QPD_E_INPUT, msg);
 }

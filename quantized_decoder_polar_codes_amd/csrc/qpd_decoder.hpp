@@ -20,6 +20,7 @@
 #include "qpd_host.hpp"
 #include "qpd_status.hpp"
 #include "qpd_list.hpp"
+#include "qpd_tx.hpp"
 
 namespace {
 
@@ -105,6 +106,7 @@ struct qpd_decoder {
     DeviceChunk mc_llr;       // qpd_mc_decode_f64: float64 LLRs of one chunk (qpd_chunk.hpp: mc_llr_chunk_frames)
     DeviceBuf mc_rec;         // qpd_mc_llr / qpd_mc_decode_f64 with rec: the reconstruction table's device copy
     std::vector<double> mc_rec_host;  // what mc_rec holds (empty: nothing)
+    std::unique_ptr<qpd_tx::Code> tx_code;  // qpd_encode_host: the encoder's constants (built at the first call)
     DeviceChunk u8_sym;       // qpd_decode_u8 / qpd_decode_llr outside pre-mode: int32 symbols of one chunk
     int64_t u8_chunk = 0;    // QPD_U8_CHUNK (tests): frames per staging chunk (0: 1 GB of int32 symbols)
     int u8_staged = 0;       // qpd_info.u8_staged: the last decode call widened its input into u8_sym

@@ -36,6 +36,6 @@ enum Kind : int32_t { K_SC_FLOAT = 0, K_SC_LUT = 1, K_SCL_LUT = 2, K_FASTSC_LUT 
 enum Dom : int32_t { DOM_LUT = 0, DOM_FLOAT = 1, DOM_UNIFORM = 2, DOM_LLOYD = 3 };
 
 // Device error flags (DevPlan/FastPlan err word).
-enum ErrFlag : int32_t { ERR_SYMBOL = 1, ERR_LLOYD = 2, ERR_NAN_PM = 4, ERR_NAN_LLR = 8 };
+enum ErrFlag : int32_t { ERR_SYMBOL = 1, ERR_LLOYD = 2, ERR_NAN_PM = 4, ERR_NAN_LLR = 8, ERR_MSG_BIT = 16 };
 
 }  // namespace qpd

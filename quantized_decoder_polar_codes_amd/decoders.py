@@ -418,6 +418,110 @@ class _DecoderBase:
         _lib.check(lib.qpd_dmetric_host(self._h, _ptr(a), B, _ptr(metric), _ptr(bits)))
         return (metric, bits) if return_bits else metric
 
+    # -- transmit side -----------------------------------------------------------
+    def _tx_args(self, crc_mask, signal: bool = True):
+        """(QpdTxArgs, the mask array it points to) of one transmit call."""
+        tx = _lib.QpdTxArgs()
+        mask = None
+        if crc_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(crc_mask).reshape(-1).astype(np.uint8))
+            tx.crc_mask, tx.crc_mask_bits = _ptr(mask), mask.size
+        tx.no_signal = 0 if signal else 1
+        return tx, mask
+
+    def encode_batch(self, msg, crc_mask=None, return_info: bool = False):
+        """Encode B messages for this decoder's code: the drivers' ``PolarEnc.encode`` (and, for
+        the CRC-aided decoders, ``CRCEnc.encode`` in front of it), batched (qpd_encode /
+        qpd_encode_host).  ``msg``: 0/1 entries, [B, A] for the CRC-aided decoders (the first K - A
+        bits of the message's CRC are appended), else [B, K].  -> codewords uint8 [B, N], or
+        ``(info [B, K], codewords)`` with ``return_info``.  ``crc_mask`` (0/1 entries, at most
+        crc_n): XORed onto the tail of the CRC before it is cut to K - A bits, the mirror of
+        ``decode_batch(..., return_status=True, crc_mask=...)``: a word encoded under a mask
+        passes the CRC only under that mask.  numpy in -> numpy out, on the host; a torch CUDA
+        uint8 tensor is read where it lies, on the current stream -> torch CUDA tensors (other
+        dtypes are converted to uint8 first).  An entry other than 0 / 1 counts as its low bit
+        and raises ValueError (numpy) or is reported by qpd_check_input_error (device)."""
+        torch = _torch()
+        lib = _lib.load()
+        tx, _mask = self._tx_args(crc_mask)
+        if torch is not None and isinstance(msg, torch.Tensor) and msg.is_cuda:
+            m = msg.reshape(-1, self.A)
+            m = (m if m.dtype == torch.uint8 else m.to(torch.uint8)).contiguous()
+            B = m.shape[0]
+            cw = torch.empty((B, self.N), dtype=torch.uint8, device=m.device)
+            info = torch.empty((B, self.K), dtype=torch.uint8, device=m.device) if return_info else None
+            stream = torch.cuda.current_stream(m.device).cuda_stream
+            _lib.check(lib.qpd_encode(self._h, ctypes.c_void_p(m.data_ptr()), B, ctypes.byref(tx),
+                                      None if info is None else ctypes.c_void_p(info.data_ptr()),
+                                      ctypes.c_void_p(cw.data_ptr()), ctypes.c_void_p(stream)))
+            return (info, cw) if return_info else cw
+        if torch is not None and isinstance(msg, torch.Tensor):
+            msg = msg.numpy()
+        m = np.ascontiguousarray(np.asarray(msg).astype(np.uint8, copy=False).reshape(-1, self.A))
+        B = m.shape[0]
+        cw = np.empty((B, self.N), dtype=np.uint8)
+        info = np.empty((B, self.K), dtype=np.uint8) if return_info else None
+        _lib.check(lib.qpd_encode_host(self._h, _ptr(m), B, ctypes.byref(tx), _ptr(info), _ptr(cw)))
+        return (info, cw) if return_info else cw
+
+    def transmit_batch(self, msg, sigma: float, seed: int, frame0: int = 0, crc_mask=None, quantizer=None,
+                       out: str = "llr", rec=None, signal: bool = True):
+        """The received frames of B messages (qpd_tx_frames): ``encode_batch(msg, crc_mask)``,
+        BPSK, AWGN of standard deviation ``sigma``, LLR = 2y / sigma^2 -- the frames
+        ``montecarlo.GpuFrames`` / ``GpuLlrFrames`` make, for messages the caller chooses.  Row b
+        is global frame ``frame0 + b`` of ``seed``: its noise is the generator's for that frame
+        id, whatever the batch.  ``out``: "llr" (float64 [B, N]; with ``rec``, one value per
+        symbol, the LLRs re-quantised to rec[symbol]), "symbols" (int32) or "symbols_u8"
+        (uint8, q <= 256) -- the symbols of ``quantizer``, a :class:`ChannelQuantizer`, which
+        "llr" needs only with ``rec``.  ``signal=False``: noise only (y = sigma * noise), an
+        empty candidate of a blind detection; ``msg`` then only gives the number of frames (an
+        int will do).  Always on the device: a torch CUDA tensor is read where it lies, on the
+        current stream -> a torch CUDA tensor; numpy in -> numpy out, through the device.
+        Decoding is a second call: ``decode_batch(transmit_batch(...))``."""
+        torch = _torch()
+        if torch is None:
+            raise RuntimeError("transmit_batch runs on the device: it needs torch")
+        kinds = {"llr": (_lib.QPD_TX_LLR_F64, torch.float64), "symbols": (_lib.QPD_TX_SYM_I32, torch.int32),
+                 "symbols_u8": (_lib.QPD_TX_SYM_U8, torch.uint8)}
+        if out not in kinds:
+            raise ValueError(f"out must be one of {sorted(kinds)}, got {out!r}")
+        ty, dtype = kinds[out]
+        if quantizer is not None and not isinstance(quantizer, ChannelQuantizer):
+            raise TypeError(f"transmit_batch takes a ChannelQuantizer, got {type(quantizer).__name__}")
+        if quantizer is None and (out != "llr" or rec is not None):
+            raise ValueError("symbols and rec need a quantizer")
+        if rec is not None and out != "llr":
+            raise ValueError("rec applies to out='llr' only")
+        ch = _lib.QpdMcChannel()
+        ch.sigma = float(sigma)
+        if quantizer is not None:
+            ch.q, ch.n_edges = quantizer.q, quantizer.edges.size
+            ch.edges, ch.lut = quantizer.edges.ctypes.data, quantizer.lut.ctypes.data
+        recp = None
+        if rec is not None:
+            recp = np.ascontiguousarray(rec, dtype=np.float64)
+            if recp.size < quantizer.q:
+                raise ValueError(f"rec must have q={quantizer.q} entries, got {recp.size}")
+        tx, _mask = self._tx_args(crc_mask, signal)
+        on_device = isinstance(msg, torch.Tensor) and msg.is_cuda
+        device = msg.device if on_device else torch.device("cuda", max(self.device, 0))
+        if isinstance(msg, (int, np.integer)):
+            if signal:
+                raise ValueError("a frame count instead of messages needs signal=False")
+            B, m = int(msg), None
+        else:
+            if not isinstance(msg, torch.Tensor):
+                msg = torch.from_numpy(np.ascontiguousarray(np.asarray(msg).astype(np.uint8, copy=False)))
+            m = msg.reshape(-1, self.A)
+            m = (m if m.dtype == torch.uint8 else m.to(torch.uint8)).to(device).contiguous()
+            B = m.shape[0]
+        frames = torch.empty((B, self.N), dtype=dtype, device=device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        _lib.check(_lib.load().qpd_tx_frames(self._h, ctypes.byref(ch), _ptr(recp), ctypes.c_uint64(int(seed)), int(frame0), B,
+                                             None if m is None else ctypes.c_void_p(m.data_ptr()), ctypes.byref(tx), ty,
+                                             ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(stream)))
+        return frames if on_device else frames.cpu().numpy()
+
     # -- LLR input of the LUT decoders ------------------------------------------
     def _llr_args(self, llr, quantizer, name):
         """(device?, contiguous [B, N] array / tensor, llr_type) of an LLR batch."""

@@ -169,6 +169,26 @@ class GpuLlrFrames:
         return msg, llr.view(B, self.dec.N)
 
 
+class GpuTxFrames:
+    """Frame source for messages the caller chooses, backed by qpd_tx_frames
+    (``decoder.transmit_batch``): GpuFrames' / GpuLlrFrames' noise for the same (seed, frame
+    id) around the caller's codewords.  ``tx(frame0, msg) -> (msg, frames)`` with ``msg`` a
+    [B, A] device tensor (frame ``frame0 + b`` carries row b), so
+    ``generate=lambda lo, n: tx(lo, source(lo, n))`` fills run_point's ``generate`` slot for a
+    message source ``source(lo, n)``.  ``out``, ``quantizer``, ``rec``, ``crc_mask`` and
+    ``signal`` as for ``transmit_batch`` (one mask for every frame; ``signal=False``: noise
+    only, ``msg`` may then be a frame count)."""
+
+    def __init__(self, decoder, sigma: float, seed: int, quantizer=None, out: str = "llr", rec=None, crc_mask=None,
+                 signal: bool = True):
+        self.dec = decoder
+        self.sigma, self.seed = float(sigma), int(seed)
+        self.kw = dict(quantizer=quantizer, out=out, rec=rec, crc_mask=crc_mask, signal=signal)
+
+    def __call__(self, frame0: int, msg):
+        return msg, self.dec.transmit_batch(msg, self.sigma, self.seed, frame0=frame0, **self.kw)
+
+
 def _frame_errors(bits, msg):
     """Per-frame bit-error counts as a 1-D int64 tensor/array."""
     try:
