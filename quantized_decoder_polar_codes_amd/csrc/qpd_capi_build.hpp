@@ -260,6 +260,7 @@ void adopt_fast_plan(qpd_decoder *d, const qpd_config *c, const Schedule &s, con
     d->r1l = H.r1l;
     d->pw1 = H.pw1;
     d->pre = H.pre;
+    d->row_lo = H.row_lo;
     d->pre_chunk = H.pre_chunk;
     for (int i = 0; i < 3; ++i) {
         d->pfx[i].nops = (int)H.pfx[i].size();

@@ -208,8 +208,9 @@ int decode_pre_mode(qpd_decoder *d, qpd::FastPlan fp, const In *d_symbols, int64
         const int pgrid = (int)std::min<int64_t>(((Bc << (fp.n - 4)) + 255) / 256, 8192);
         void *pargs[] = {&fp, &sym, &Bc, &pre};
         rc = timed_launch(d, QPD_KC_PRE, st, [&]() -> int {
-            QPD_HIP(hipLaunchKernel(reinterpret_cast<const void *>(&qpd::root_pre_kernel<In>), dim3(pgrid), dim3(256),
-                                    pargs, 0, st));
+            const void *pk = d->row_lo ? reinterpret_cast<const void *>(&qpd::root_pre_kernel<In, true>)
+                                       : reinterpret_cast<const void *>(&qpd::root_pre_kernel<In, false>);
+            QPD_HIP(hipLaunchKernel(pk, dim3(pgrid), dim3(256), pargs, 0, st));
             QPD_HIP(hipGetLastError());
             return QPD_OK;
         });

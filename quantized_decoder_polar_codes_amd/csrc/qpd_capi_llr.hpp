@@ -70,6 +70,9 @@ const void *llr_kernel(int form, bool coop) {
         case qpd::LLR_PRE:
             return coop ? reinterpret_cast<const void *>(&qpd::llr_front_kernel<T, qpd::LLR_PRE, true>)
                         : reinterpret_cast<const void *>(&qpd::llr_front_kernel<T, qpd::LLR_PRE, false>);
+        case qpd::LLR_PRE_LO:
+            return coop ? reinterpret_cast<const void *>(&qpd::llr_front_kernel<T, qpd::LLR_PRE_LO, true>)
+                        : reinterpret_cast<const void *>(&qpd::llr_front_kernel<T, qpd::LLR_PRE_LO, false>);
         case qpd::LLR_I32: return reinterpret_cast<const void *>(&qpd::llr_front_kernel<T, qpd::LLR_I32, false>);
         default: return reinterpret_cast<const void *>(&qpd::llr_front_kernel<T, qpd::LLR_U8, false>);
     }
@@ -83,7 +86,7 @@ int llr_front(qpd_decoder *d, qpd::LlrFront C, const void *llr, int32_t type, in
     C.vec = ((uintptr_t)llr & 15u) == 0;  // N is even, N >= 16 in LLR_PRE: rows, halves and groups keep the base's alignment
     C.out_vec = ((uintptr_t)out & (uintptr_t)(epl - 1)) == 0;
     // LLR_PRE: one thread per output word; else one per 16 bytes of LLRs, four in flight
-    const int64_t work = form == qpd::LLR_PRE ? (Bc << (d->n - 4)) : (Bc * d->N / epl + 3) / 4;
+    const int64_t work = form == qpd::LLR_PRE || form == qpd::LLR_PRE_LO ? (Bc << (d->n - 4)) : (Bc * d->N / epl + 3) / 4;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, 8192));
     const void *kfn = type == QPD_LLR_F32 ? llr_kernel<float>(form, d->llr_coop) : llr_kernel<double>(form, d->llr_coop);
     void *args[] = {&C, &llr, &Bc, &out};
@@ -112,7 +115,8 @@ int decode_llr_impl(qpd_decoder *d, const qpd_mc_channel *ch, const void *d_llr,
     const size_t row = (size_t)d->N * llr_size(type);
     for (int64_t f0 = 0; f0 < B; f0 += chunk) {
         const int64_t Bc = std::min<int64_t>(chunk, B - f0);
-        if ((rc = llr_front(d, C, (const char *)d_llr + f0 * row, type, Bc, buf, pre ? qpd::LLR_PRE : qpd::LLR_I32, st)))
+        if ((rc = llr_front(d, C, (const char *)d_llr + f0 * row, type, Bc, buf,
+                            pre ? (d->row_lo ? qpd::LLR_PRE_LO : qpd::LLR_PRE) : qpd::LLR_I32, st)))
             return rc;
         uint8_t *out = d_out + f0 * d->out_bits;
         rc = pre ? decode_pre_rows(d, (const uint32_t *)buf, Bc, out, st) : decode_impl(d, (const int32_t *)buf, Bc, out, st);

@@ -130,6 +130,7 @@ const void *mc_kernel(int mode) {
     switch (mode) {
         case qpd::MC_SYM: return reinterpret_cast<const void *>(&qpd::mc_frames_kernel<qpd::MC_SYM>);
         case qpd::MC_PRE: return reinterpret_cast<const void *>(&qpd::mc_frames_kernel<qpd::MC_PRE>);
+        case qpd::MC_PRE_LO: return reinterpret_cast<const void *>(&qpd::mc_frames_kernel<qpd::MC_PRE_LO>);
         case qpd::MC_LLR: return reinterpret_cast<const void *>(&qpd::mc_frames_kernel<qpd::MC_LLR>);
         default: return reinterpret_cast<const void *>(&qpd::mc_frames_kernel<qpd::MC_LLR_REC>);
     }
@@ -214,7 +215,7 @@ int mc_decode(qpd_decoder *d, const qpd_mc_channel *ch, uint64_t seed, int64_t f
     void *buf = fused ? d->pre_rows.p : d->mc_sym.p;
     for (int64_t f0 = 0; f0 < B; f0 += chunk) {
         const int64_t Bc = std::min<int64_t>(chunk, B - f0);
-        int r = mc_launch(d, ch, seed, frame0 + f0, Bc, d_msg + f0 * d->out_bits, buf, fused ? qpd::MC_PRE : qpd::MC_SYM, st);
+        int r = mc_launch(d, ch, seed, frame0 + f0, Bc, d_msg + f0 * d->out_bits, buf, fused ? (d->row_lo ? qpd::MC_PRE_LO : qpd::MC_PRE) : qpd::MC_SYM, st);
         if (r) return r;
         uint8_t *out = d_out + f0 * d->out_bits;
         r = fused ? decode_pre_rows(d, (const uint32_t *)buf, Bc, out, st)

@@ -100,6 +100,7 @@ struct qpd_decoder {
     bool r1l = false;  // fast engine: an R1 node needs r1_large (the R1L instantiation)
     bool pw1 = false;  // fast engine: one pointer word per path (compact_pointer_fields)
     bool pre = false;         // fast engine pre-mode: root_pre_kernel, then the decode on its rows
+    bool row_lo = false;      // ... whose rows are in lookup order (FastHostPlan::row_lo)
     int64_t pre_chunk = 0;    // frames per pre-pass chunk
     DeviceChunk pre_rows;     // pre-pass rows of one chunk (N bytes per frame)
     DeviceChunk mc_sym;       // qpd_mc_decode without a fused pre-pass: int32 symbols of one chunk

@@ -93,6 +93,9 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
     // one-pointer-word SCL-LUT instantiations run only op lists with the pre-pass
     // (plan_fast; +1.1 % SCL-LUT, -1.3 % when FastSCL-LUT's dropped them too, r05z5)
     constexpr bool kChan = !(PW1 && KIND == K_SCL_LUT);
+    // rows in lookup order (QPD_ROW_BYTEIDX, qpd_fast_switches.hpp): the plain kinds; plan_fast
+    // marks their ops MF_LO by the same rule (FastHostPlan::row_lo)
+    constexpr bool kLO = QPD_ROW_BYTEIDX != 0 && (KIND == K_SC_LUT || KIND == K_SCL_LUT);
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[];
     // list kinds at two frame sets: the f / g ops' byte tables (stage_tab) and the
     // folded descents (MF_FF), 768 B at the start of the wave's LDS -- a constant
@@ -237,7 +240,7 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
                             break;
                         }
                     }
-                    bot3_op<kList, LM, kLazy, kLdsTab, kChan>(P, Mv, op, yv, stv, cur.T, cur.T2, gl, gbase, L, sel_all, sstride, lane, [&]() {
+                    bot3_op<kList, LM, kLazy, kLdsTab, kChan, kLO>(P, Mv, op, yv, stv, cur.T, cur.T2, gl, gbase, L, sel_all, sstride, lane, [&]() {
                         if (oi + 1 < P.nops) pre = fetch_pre(P, nxt, lane, vlane);
                     }, tb);
                     break;
@@ -254,7 +257,7 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
                             const int key = ((fl & MF_DST_LDS) ? 1 : 0) | ((fl & MF_FF_DL) ? 2 : 0);
                             stage_tab(tb, cur.T, op.type == OP_F ? (lane & 31) : gtab_dw(lane));
                             stage_tab(tb + 512, cur.T2, lane & 31);
-#define QPD_FF(G, D_, C_) ff_op<G, D_, C_, NS>(Mv, op, src, usrc, tb, lane)
+#define QPD_FF(G, D_, C_) ff_op<G, D_, C_, NS, kLO>(Mv, op, src, usrc, tb, lane)
                             if (op.type == OP_F) {
                                 if (key == 0) QPD_FF(false, 0, 0);
                                 else if (key == 2) QPD_FF(false, 0, 1);
@@ -271,13 +274,13 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
                         }
                     }
                     if (fl & MF_GSEL)
-                        gsel_op(Mv, op, yv, usrc, lane);
+                        gsel_op<NS, kLO>(Mv, op, yv, usrc, lane);
                     else if (NS >= 2 && !(fl & (MF_CHAN | MF_PRE))) {  // (one-set FastSCL: smaller code measured faster)
                         // row spaces of source and destination fixed per instantiation
                         const int key = ((fl & MF_SRC_LDS) ? 1 : 0) | ((fl & MF_DST_LDS) ? 2 : 0);
                         if constexpr (kLdsTab)
                             if (op.cnt >= 8) stage_tab(tb, cur.T, op.type == OP_F ? (lane & 31) : gtab_dw(lane));
-#define QPD_FG(G, S_, D_) fg_op<G, true, NS, S_, D_, kLdsTab>(P, Mv, op, yv, src, usrc, cur.T, lane, tb)
+#define QPD_FG(G, S_, D_) fg_op<G, true, NS, S_, D_, kLdsTab, kLO>(P, Mv, op, yv, src, usrc, cur.T, lane, tb)
                         // (S[d] in LDS puts S[d + 1] in LDS too: no key 1 variant)
                         if (op.type == OP_F) {
                             if (key == 0) QPD_FG(false, 0, 0);
@@ -290,12 +293,12 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
                         }
 #undef QPD_FG
                     } else if (kChan && (fl & MF_CHAN)) {
-                        if (op.type == OP_F) fg_chan_op<false>(P, Mv, op, yv, usrc, cur.T, lane);
-                        else fg_chan_op<true>(P, Mv, op, yv, usrc, cur.T, lane);
+                        if (op.type == OP_F) fg_chan_op<false, NS, kLO>(P, Mv, op, yv, usrc, cur.T, lane);
+                        else fg_chan_op<true, NS, kLO>(P, Mv, op, yv, usrc, cur.T, lane);
                     } else if (op.type == OP_F)
-                        fg_op<false, false>(P, Mv, op, yv, src, usrc, cur.T, lane);
+                        fg_op<false, false, NS, -1, -1, false, kLO>(P, Mv, op, yv, src, usrc, cur.T, lane);
                     else
-                        fg_op<true, false>(P, Mv, op, yv, src, usrc, cur.T, lane);
+                        fg_op<true, false, NS, -1, -1, false, kLO>(P, Mv, op, yv, src, usrc, cur.T, lane);
 #pragma unroll
                     for (int s = 0; s < NS; ++s) stv[s].ps = pset(stv[s].ps, op.sh_dst, gl);
                     break;

@@ -102,12 +102,15 @@ __device__ __forceinline__ void bot_pair(Path (&st)[NS], uint32_t (&x)[NS][2], u
 // `prefetch_next` issues the next op's operand prefetch at the start of stage
 // D instead of at the start of this op (4 registers less through stages A-C).
 // LT: the folded parent's lookups (MF_BFG) from its table staged as bytes at tb (lut_lds).
-template <bool kList, int LM, bool LAZY, bool LT, bool CH, int NS, class PF, class Path>
+// LO (rows in lookup order, QPD_ROW_BYTEIDX): a row or pre-pass row of 8 symbols is W3 in
+// interleaved order as it lies, the folded parent's 16 symbols two index words.
+template <bool kList, int LM, bool LAZY, bool LT, bool CH, bool LO, int NS, class PF, class Path>
 __device__ __forceinline__ void bot3_op(const FastPlan &P, const Mem (&M)[NS], const MOp &op,
                                         const int32_t *const (&y)[NS], Path (&st)[NS], uint32_t Tf0, uint32_t T2, int gl,
                                         int gbase, int L, int *sel, int sstride, int lane, PF &&prefetch_next,
                                         uint8_t *tb) {
     constexpr bool BI = QPD_BOT3_BYTEIDX != 0;
+    static_assert(BI || !LO, "QPD_ROW_BYTEIDX needs QPD_BOT3_BYTEIDX: a row of 8 symbols is held as BOT3 holds W3");
     const int p0 = op.tab * QPD_EXP_TABMUL;
     const int fr = op.cnt;
     const uint32_t *ft = P.f_tab, *gt = P.g_tab;
@@ -147,12 +150,20 @@ __device__ __forceinline__ void bot3_op(const FastPlan &P, const Mem (&M)[NS], c
             const uint32_t a = M[s].ld(sl, op.src_row, src), b = M[s].ld(sl, op.src_row + 1, src);
             const uint32_t ub = (op.flags & MF_BG) ? M[s].ld(ul, op.u_row, gbase + pfield(st[s].U(), op.sh_u)) : 0u;
             // (ub = 0 for f: entries < 256); the parent's lookup places W3's nibbles where BOT3 wants them
+            if constexpr (LO) {  // (U[n-3]'s bits 0-3 / 4-7: the halves of a's / b's elements)
+                x[s][0] = LT ? lut_lds<8, true, 0, true, true>(a, b, ub, ub >> 4) : lut_vec<8, true, true>(T2, a, b, ub, ub >> 4);
+                continue;
+            }
             x[s][0] = LT ? lut_lds<8, true, 0, BI>(a, b, ub) : lut_vec<8, BI>(T2, a, b, ub);
         }
     } else {
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             x[s][0] = sym_word<CH>(P, M[s], op, y[s], gbase + pfield(st[s].ps, op.sh_src), 0);  // W3
+            if constexpr (LO) {  // a row is in that order already; the channel (N = 8) is permuted once
+                if (CH && (op.flags & MF_CHAN)) x[s][0] = nib_interleave8(x[s][0]);
+                continue;
+            }
             if constexpr (BI) x[s][0] = nib_interleave8(x[s][0]);  // from a row / the channel: permuted once
         }
     }

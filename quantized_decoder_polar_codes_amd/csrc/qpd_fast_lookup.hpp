@@ -76,6 +76,23 @@ __device__ __forceinline__ uint32_t chan_word8(const int32_t *y, int e0, bool ve
     return w;
 }
 
+// Channel symbols e0..e0+3 (nibbles 0-3) and e1..e1+3 (nibbles 4-7), e0 and e1 multiples
+// of 4: the two runs of a word of a row in lookup order (QPD_ROW_BYTEIDX).
+__device__ __forceinline__ uint32_t chan_word44(const int32_t *y, int e0, int e1, bool vec, int v, int32_t *err) {
+    if (!vec) return chan_word(y, e0, 4, v, err) | (chan_word(y, e1, 4, v, err) << 16);
+    const int4 a = *(const int4 *)(y + e0), b = *(const int4 *)(y + e1);
+    const int e[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    uint32_t w = 0, bad = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t s = (uint32_t)e[i];
+        bad |= s >= (uint32_t)v;
+        w |= (s >= (uint32_t)v ? 0u : s) << (4 * i);
+    }
+    if (bad) atomicOr(err, 1);
+    return w;
+}
+
 // The same from uint8 input (qpd_decode_u8; read by root_pre_kernel only, so v <= 16).
 // `vec` = the input rows are 8-byte aligned: the eight symbols are one 64-bit
 // load, range-checked and packed SWAR.  A byte is out of range when its high
@@ -99,9 +116,8 @@ __device__ __forceinline__ uint32_t nib_pack4(uint32_t x) {  // bytes 0-3 of x (
     return (t | (t >> 8)) & 0xFFFFu;
 }
 
-__device__ __forceinline__ uint32_t chan_word8(const uint8_t *y, int e0, bool vec, int v, int32_t *err) {
-    if (!vec) return chan_word(y, e0, 8, v, err);
-    const uint2 x = *(const uint2 *)(y + e0);
+// Eight symbols as the bytes of x: range-checked and packed SWAR (see above).
+__device__ __forceinline__ uint32_t chan_pack8(uint2 x, int v, int32_t *err) {
     const uint32_t k = (uint32_t)(16 - v) * 0x01010101u;
     uint32_t lo0 = x.x & 0x0F0F0F0Fu, lo1 = x.y & 0x0F0F0F0Fu;
     // bits 7:4 of each byte: the high nibble, or the carry of low nibble + 16 - v
@@ -115,6 +131,16 @@ __device__ __forceinline__ uint32_t chan_word8(const uint8_t *y, int e0, bool ve
         atomicOr(err, 1);
     }
     return nib_pack4(lo0) | (nib_pack4(lo1) << 16);
+}
+
+__device__ __forceinline__ uint32_t chan_word8(const uint8_t *y, int e0, bool vec, int v, int32_t *err) {
+    if (!vec) return chan_word(y, e0, 8, v, err);
+    return chan_pack8(*(const uint2 *)(y + e0), v, err);
+}
+
+__device__ __forceinline__ uint32_t chan_word44(const uint8_t *y, int e0, int e1, bool vec, int v, int32_t *err) {
+    if (!vec) return chan_word(y, e0, 4, v, err) | (chan_word(y, e1, 4, v, err) << 16);
+    return chan_pack8(make_uint2(*(const uint32_t *)(y + e0), *(const uint32_t *)(y + e1)), v, err);
 }
 
 // Word w (8 symbols) of S[d] of the path whose slot is `src`.
@@ -158,8 +184,34 @@ __device__ __forceinline__ uint32_t sym_word(const FastPlan &P, const Mem &M, co
 template <int NE>
 __device__ constexpr int il_nib(int k) { return k < NE / 2 ? 2 * k + 1 : 2 * (k - NE / 2); }
 
-template <int NE, bool IL = false>
-__device__ __forceinline__ uint32_t lut_vec(uint32_t T, uint32_t A, uint32_t B, uint32_t hi) {
+// Bit k of c (c < 16) -> bit 8k: one 24-bit multiply (full rate) copies c to distances
+// 7, 14, 21; no two copies' bits meet, so nothing carries.
+__device__ __forceinline__ uint32_t byte_bits4(uint32_t c) { return __umul24(c, 0x204081u) & 0x01010101u; }
+
+// LO (NE = 8; rows in lookup order, QPD_ROW_BYTEIDX): A and B are two words of a row
+// in that order, so their bytes are the eight indices as they lie -- element k < 4 is
+// byte k of A, element k >= 4 byte k - 4 of B, table half bit k of `hi` as ever -- and
+// no X / Y is built.  With IL the result is the child row's word in lookup order.
+template <int NE, bool IL = false, bool LO = false>
+__device__ __forceinline__ uint32_t lut_vec(uint32_t T, uint32_t A, uint32_t B, uint32_t hi, uint32_t hi2 = 0u) {
+    static_assert(!LO || NE == 8, "LO: whole words of a row in lookup order");
+    if constexpr (LO) {  // (table halves: bits 0-3 of hi for A's elements, of hi2 for B's)
+        const uint32_t ha = byte_bits4(hi & 15u) << 7, hb = byte_bits4(hi2 & 15u) << 7;
+        const uint32_t AA = ((A >> 1) & 0x7F7F7F7Fu) | ha, BA = ((B >> 1) & 0x7F7F7F7Fu) | hb;
+        const uint32_t AS = (A << 2) & 0x1C1C1C1Cu, BS = (B << 2) & 0x1C1C1C1Cu;
+        uint32_t out = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int j = k & 3;
+            const uint32_t WA = k < 4 ? AA : BA, WS = k < 4 ? AS : BS;
+            const uint32_t v = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(WA >> (8 * j)), (int)T);
+            out |= __builtin_amdgcn_ubfe(v, WS >> (8 * j), 4) << (4 * (IL ? il_nib<NE>(k) : k));
+#if QPD_VEC_CHAIN
+            if (k + 1 < NE) asm("" : "+v"(out));
+#endif
+        }
+        return out;
+    }
     const uint32_t X = ((A << 4) & 0xF0F0F0F0u) | (B & 0x0F0F0F0Fu);
     const uint32_t Y = (A & 0xF0F0F0F0u) | ((B >> 4) & 0x0F0F0F0Fu);
     uint32_t hx = 0, hy = 0;  // bit 2j / 2j+1 of hi -> bit 8j+7
@@ -266,13 +318,19 @@ __device__ __forceinline__ int gtab_dw(int lane) { return lane ^ ((lane >> 5) * 
 // kernel declares no static LDS before them): the lookups address LDS through a
 // constant, which the compiler folds into each ds_read_u8's offset field.
 typedef __attribute__((address_space(3))) const uint8_t lds_u8;
-template <int NE, bool ISG, int TOFF = 0, bool IL = false>
-__device__ __forceinline__ uint32_t lut_lds(uint32_t A, uint32_t B, uint32_t hi) {
+// LO (NE = 8; as lut_vec): A / B are the index words of elements 0-3 / 4-7 as they
+// lie in a row in lookup order, bits 0-3 of `hi` / of `hi2` their table halves.
+template <int NE, bool ISG, int TOFF = 0, bool IL = false, bool LO = false>
+__device__ __forceinline__ uint32_t lut_lds(uint32_t A, uint32_t B, uint32_t hi, uint32_t hi2 = 0u) {
+    static_assert(!LO || (NE == 8 && QPD_GSWZ == 0), "LO: whole words of a row in lookup order");
     lds_u8 *const tb = (lds_u8 *)(size_t)TOFF;
-    uint32_t X = ((A << 4) & 0xF0F0F0F0u) | (B & 0x0F0F0F0Fu);
-    uint32_t Y = (A & 0xF0F0F0F0u) | ((B >> 4) & 0x0F0F0F0Fu);
-    uint32_t hx = 0, hy = 0;  // byte j = bit 2j / 2j+1 of hi (g: the u half)
-    if constexpr (ISG) {
+    uint32_t X = LO ? A : ((A << 4) & 0xF0F0F0F0u) | (B & 0x0F0F0F0Fu);
+    uint32_t Y = LO ? B : (A & 0xF0F0F0F0u) | ((B >> 4) & 0x0F0F0F0Fu);
+    uint32_t hx = 0, hy = 0;  // byte j = bit 2j / 2j+1 of hi (g: the u half); LO: bit j of hi / hi2
+    if constexpr (ISG && LO) {
+        hx = byte_bits4(hi & 15u);
+        hy = byte_bits4(hi2 & 15u);
+    } else if constexpr (ISG) {
         hx = (((hi & 0x55u) * 0x02082080u) >> 7) & 0x01010101u;
         hy = ((((hi >> 1) & 0x55u) * 0x02082080u) >> 7) & 0x01010101u;
         if constexpr (QPD_GSWZ != 0) {  // bytes of hx, hy are 0 / 1: X ^= hx * M by shifts (a
@@ -290,15 +348,16 @@ __device__ __forceinline__ uint32_t lut_lds(uint32_t A, uint32_t B, uint32_t hi)
 #if QPD_LUT_OPAQUE_XY
     // the words whole: otherwise the compiler rebuilds each index's byte from A and B
     // (v_and + v_bitop3 chains) beside X / Y themselves -- 15 VALU for 8 f indices, not 12
-    asm("" : "+v"(X), "+v"(Y));
+    if constexpr (!LO) asm("" : "+v"(X), "+v"(Y));
 #endif
     uint32_t idx[NE];
 #pragma unroll
     for (int k = 0; k < NE; ++k) {
-        const int j = k >> 1;
-        const uint32_t W = (k & 1) ? Y : X;
+        const int j = LO ? (k & 3) : (k >> 1);
+        const bool second = LO ? k >= 4 : (k & 1) != 0;
+        const uint32_t W = second ? Y : X;
         if constexpr (ISG)  // byte 0 = byte j of W, byte 1 = byte j of the u bits, bytes 2-3 = 0
-            idx[k] = __builtin_amdgcn_perm((k & 1) ? hy : hx, W, (uint32_t)(j | ((4 + j) << 8) | (0x0C << 16) | (0x0C << 24)));
+            idx[k] = __builtin_amdgcn_perm(second ? hy : hx, W, (uint32_t)(j | ((4 + j) << 8) | (0x0C << 16) | (0x0C << 24)));
         else
             idx[k] = __builtin_amdgcn_ubfe(W, 8 * j, 8);
 #if QPD_EXP_LUTMASK != 0xFFFF
@@ -352,12 +411,31 @@ __device__ __forceinline__ uint32_t fg_word(const FastPlan &P, const Mem &M, con
 // f / g op at the root on the channel symbols (MF_CHAN: codes without the
 // root pre-pass), a rolled loop over its words -- one copy of the channel
 // reads (range check, error flag) instead of one per unrolled word.
-template <bool ISG, int NS>
+// LO: S[1] is written in lookup order -- word w from the channel's four runs of four
+// symbols at 4w, 4 (nwo + w), 4 (2 nwo + w), 4 (3 nwo + w).
+template <bool ISG, int NS, bool LO = false>
 __device__ __forceinline__ void fg_chan_op(const FastPlan &P, const Mem (&M)[NS], const MOp &op, const int32_t *const (&y)[NS],
                                            const int (&usrc)[NS], uint32_t T, int lane) {
     const int ctemp = op.cnt;
     const bool dl = op.flags & MF_DST_LDS, ul = op.flags & MF_U_LDS;
-    if (ctemp >= 8) {
+    if (LO && ctemp >= 8) {
+        const int nwo = ctemp >> 3;
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll 1
+            for (int w = 0; w < nwo; ++w) {
+                const uint32_t a = chan_word(y[s], 4 * w, 4, P.v, P.err) | (chan_word(y[s], 4 * (nwo + w), 4, P.v, P.err) << 16);
+                const uint32_t b = chan_word(y[s], 4 * (2 * nwo + w), 4, P.v, P.err) |
+                                   (chan_word(y[s], 4 * (3 * nwo + w), 4, P.v, P.err) << 16);
+                uint32_t ub = 0u;
+                if (ISG) {
+                    const int ba = 4 * w, bb = 4 * (nwo + w);  // u bits of the word's high- / low-nibble elements
+                    ub = ((M[s].ld(ul, op.u_row + (ba >> 5), usrc[s]) >> (ba & 31)) & 15u) |
+                         (((M[s].ld(ul, op.u_row + (bb >> 5), usrc[s]) >> (bb & 31)) & 15u) << 4);
+                }
+                M[s].st(dl, op.dst_row + w, lane, lut_vec<8, true>(T, a, b, ub));
+            }
+    } else if (ctemp >= 8) {
         const int nwo = ctemp >> 3;
 #pragma unroll
         for (int s = 0; s < NS; ++s)
@@ -380,7 +458,10 @@ __device__ __forceinline__ void fg_chan_op(const FastPlan &P, const Mem (&M)[NS]
 }
 
 // LT: lookups from the byte table staged at tb (lut_lds) instead of T.
-template <bool ISG, bool RAW, int NS, int SL = -1, int DL = -1, bool LT = false>
+// LO (rows in lookup order, QPD_ROW_BYTEIDX): S[d] and S[d+1] (>= 8 symbols each) are in
+// that order; the same word pairs (w, nwo + w) are read, as index words, and the u bits of
+// output word w are bits 4w .. 4w+3 and 4 (nwo + w) .. of U[d+1].
+template <bool ISG, bool RAW, int NS, int SL = -1, int DL = -1, bool LT = false, bool LO = false>
 __device__ __forceinline__ void fg_op(const FastPlan &P, const Mem (&M)[NS], const MOp &op, const int32_t *const (&y)[NS],
                                       const int (&src)[NS], const int (&usrc)[NS], uint32_t T, int lane,
                                       const uint8_t *tb = nullptr) {
@@ -391,7 +472,7 @@ __device__ __forceinline__ void fg_op(const FastPlan &P, const Mem (&M)[NS], con
         if constexpr (NS >= 2) {
             // chunks of 4 words of both sets: the sets' loads are in flight together
             for (int w0 = 0; w0 < nwo; w0 += 4) {
-                uint32_t A[NS][4], B[NS][4], ub[NS];
+                uint32_t A[NS][4], B[NS][4], ub[NS], ub2[NS];
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
 #pragma unroll
@@ -399,15 +480,28 @@ __device__ __forceinline__ void fg_op(const FastPlan &P, const Mem (&M)[NS], con
                         A[s][k] = fg_word<RAW, SL>(P, M[s], op, y[s], src[s], w0 + k);
                         B[s][k] = fg_word<RAW, SL>(P, M[s], op, y[s], src[s], nwo + w0 + k);
                     }
-                    ub[s] = ISG ? M[s].ld(ul, op.u_row + (w0 >> 2), usrc[s]) : 0u;
+                    ub[s] = ub2[s] = 0u;
+                    if constexpr (ISG && LO) {  // 16 bits each, at bit 0 or 16 of their words (nwo a multiple of 8)
+                        ub[s] = M[s].ld(ul, op.u_row + (w0 >> 3), usrc[s]) >> ((w0 & 4) << 2);
+                        ub2[s] = M[s].ld(ul, op.u_row + ((nwo + w0) >> 3), usrc[s]) >> ((w0 & 4) << 2);
+                    } else if constexpr (ISG) {
+                        ub[s] = M[s].ld(ul, op.u_row + (w0 >> 2), usrc[s]);
+                    }
                 }
 #pragma unroll
                 for (int s = 0; s < NS; ++s)
 #pragma unroll
-                    for (int k = 0; k < 4; ++k)
+                    for (int k = 0; k < 4; ++k) {
+                        if constexpr (LO) {
+                            M[s].st(dl, op.dst_row + w0 + k, lane,
+                                    LT ? lut_lds<8, ISG, 0, true, true>(A[s][k], B[s][k], ub[s] >> (k << 2), ub2[s] >> (k << 2))
+                                       : lut_vec<8, true, true>(T, A[s][k], B[s][k], ub[s] >> (k << 2), ub2[s] >> (k << 2)));
+                            continue;
+                        }
                         M[s].st(dl, op.dst_row + w0 + k, lane,
                                 LT ? lut_lds<8, ISG>(A[s][k], B[s][k], ub[s] >> (k << 3))
                                    : lut_vec<8>(T, A[s][k], B[s][k], ub[s] >> (k << 3)));
+                    }
             }
         } else {
             for (int w0 = 0; w0 < nwo; w0 += 8) {
@@ -417,13 +511,21 @@ __device__ __forceinline__ void fg_op(const FastPlan &P, const Mem (&M)[NS], con
                     A[k] = fg_word<RAW, SL>(P, M[0], op, y[0], src[0], w0 + k);
                     B[k] = fg_word<RAW, SL>(P, M[0], op, y[0], src[0], nwo + w0 + k);
                 }
-                if (ISG) {
+                if (ISG && LO) {  // u bits 4 w0 .. and 4 (nwo + w0) ..: one word each
+                    ub[0] = M[0].ld(ul, op.u_row + (w0 >> 3), usrc[0]);
+                    ub[1] = M[0].ld(ul, op.u_row + ((nwo + w0) >> 3), usrc[0]);
+                } else if (ISG) {
                     ub[0] = M[0].ld(ul, op.u_row + (w0 >> 2), usrc[0]);
                     ub[1] = M[0].ld(ul, op.u_row + (w0 >> 2) + 1, usrc[0]);
                 }
 #pragma unroll
-                for (int k = 0; k < 8; ++k)
+                for (int k = 0; k < 8; ++k) {
+                    if constexpr (LO) {
+                        M[0].st(dl, op.dst_row + w0 + k, lane, lut_vec<8, true, true>(T, A[k], B[k], ub[0] >> (k << 2), ub[1] >> (k << 2)));
+                        continue;
+                    }
                     M[0].st(dl, op.dst_row + w0 + k, lane, lut_vec<8>(T, A[k], B[k], ub[k >> 2] >> ((k & 3) << 3)));
+                }
             }
         }
     } else if (ctemp >= 8) {
@@ -445,10 +547,18 @@ __device__ __forceinline__ void fg_op(const FastPlan &P, const Mem (&M)[NS], con
         for (int s = 0; s < NS; ++s)
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (k < nwo)
+                if (k < nwo) {
+                    if constexpr (LO) {  // U[d+1] is one word: bits 4k .. and 4 (nwo + k) ..
+                        const uint32_t h2 = ub[s] >> (nwo << 2);
+                        M[s].st(dl, op.dst_row + k, lane,
+                                LT ? lut_lds<8, ISG, 0, true, true>(A[s][k], B[s][k], ub[s] >> (k << 2), h2 >> (k << 2))
+                                   : lut_vec<8, true, true>(T, A[s][k], B[s][k], ub[s] >> (k << 2), h2 >> (k << 2)));
+                        continue;
+                    }
                     M[s].st(dl, op.dst_row + k, lane,
                             LT ? lut_lds<8, ISG>(A[s][k], B[s][k], ub[s] >> (k << 3))
                                : lut_vec<8>(T, A[s][k], B[s][k], ub[s] >> (k << 3)));
+                }
     } else {  // ctemp in {2, 4}: the whole depth-d node (a then b) is one word
         uint32_t W[NS], ub[NS];
 #pragma unroll
@@ -471,11 +581,53 @@ __device__ __forceinline__ void fg_op(const FastPlan &P, const Mem (&M)[NS], con
 // a re-read of the row just stored (S[d+1] is still stored: the child's g
 // reads it later).  Chunks of two S[d+2] words per set; S[d] in the slab.
 // The op's table is staged at tb, the child's f table at tb + 512 (lut_lds).
-template <bool ISG, int DL, int CDL, int NS>
+// LO (rows in lookup order): the same words are read and written; S[d+1]'s words u and
+// u + nwc, in lookup order, are the index words of S[d+2]'s word u as they lie.
+template <bool ISG, int DL, int CDL, int NS, bool LO = false>
 __device__ __forceinline__ void ff_op(const Mem (&M)[NS], const MOp &op, const int (&src)[NS], const int (&usrc)[NS],
                                       const uint8_t *tb, int lane) {
     const int nwo = op.cnt >> 3, nwc = nwo >> 1;  // nwc even (op.cnt >= 32)
     const bool ul = op.flags & MF_U_LDS;
+    if constexpr (LO) {
+        for (int u0 = 0; u0 < nwc; u0 += 2) {
+            // u bits of word w: 4w .. 4w+3 and 4 (nwo + w) ..; the chunk's words u0, u0 + 1 (u0
+            // even: one u word and shift) and nwc + u0, nwc + u0 + 1
+            uint32_t A[NS][4], B[NS][4], ua[NS][2], ub[NS][2], X[NS][4];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int w = (k < 2 ? 0 : nwc) + u0 + (k & 1);
+                    A[s][k] = M[s].ld(false, op.src_row + w, src[s]);
+                    B[s][k] = M[s].ld(false, op.src_row + nwo + w, src[s]);
+                }
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    ua[s][h] = ub[s][h] = 0u;
+                    if (ISG) {
+                        const int w = (h ? nwc : 0) + u0;
+                        ua[s][h] = M[s].ld(ul, op.u_row + (w >> 3), usrc[s]) >> ((w & 7) << 2);
+                        ub[s][h] = M[s].ld(ul, op.u_row + ((nwo + w) >> 3), usrc[s]) >> (((nwo + w) & 7) << 2);
+                    }
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int w = (k < 2 ? 0 : nwc) + u0 + (k & 1);
+                    X[s][k] = lut_lds<8, ISG, 0, true, true>(A[s][k], B[s][k], ua[s][k >> 1] >> ((k & 1) << 2),
+                                                             ub[s][k >> 1] >> ((k & 1) << 2));
+                    M[s].st(DL != 0, op.dst_row + w, lane, X[s][k]);
+                }
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+#pragma unroll
+                for (int k = 0; k < 2; ++k)
+                    M[s].st(CDL != 0, op.r_row + u0 + k, lane, lut_lds<8, false, 512, true, true>(X[s][k], X[s][k + 2], 0u));
+        }
+        return;
+    }
     for (int u0 = 0; u0 < nwc; u0 += 2) {
         uint32_t A[NS][4], B[NS][4], ub[NS][2], X[NS][4];
 #pragma unroll
@@ -520,11 +672,40 @@ __device__ __forceinline__ uint32_t nib_mask(uint32_t b) {
 // Root g in pre-mode (MF_GSEL; SCLLUTDecoder.cpp:157-164 at depth 0): the
 // pre-pass row holds g(y, 0) and g(y, 1) of every root position, so the
 // path's symbols are a nibble select by its left-half partial sums u.
-template <int NS>
+// LO (rows in lookup order): the pre-pass rows and S[1] are in that order, so word w's
+// high nibbles select by u bits 4w .. 4w+3 and its low ones by bits 4 (nwo + w) ..
+template <int NS, bool LO = false>
 __device__ __forceinline__ void gsel_op(const Mem (&M)[NS], const MOp &op, const int32_t *const (&y)[NS],
                                         const int (&usrc)[NS], int lane) {
     const int nwo = op.cnt >> 3;  // 1, 2, 4 or a multiple of 8
     const bool dl = op.flags & MF_DST_LDS, ul = op.flags & MF_U_LDS;
+    if constexpr (LO) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const uint32_t *g = (const uint32_t *)y[s] + op.src_row;
+            for (int w0 = 0; w0 < nwo; w0 += 8) {
+                uint32_t g0[8], g1[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    g0[k] = g1[k] = 0u;
+                    if (k == 0 || w0 + k < nwo) {
+                        g0[k] = g[w0 + k];
+                        g1[k] = g[nwo + w0 + k];
+                    }
+                }
+                // nwo < 8: U[1] is one word (w0 = 0), the low nibbles' bits from 4 nwo on
+                const uint32_t ua = M[s].ld(ul, op.u_row + (w0 >> 3), usrc[s]);
+                const uint32_t ub = M[s].ld(ul, op.u_row + ((nwo + w0) >> 3), usrc[s]) >> ((nwo << 2) & 31);
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if (k == 0 || w0 + k < nwo) {
+                        const uint32_t m = ((byte_bits4((ua >> (k << 2)) & 15u) << 4) | byte_bits4((ub >> (k << 2)) & 15u)) * 15u;
+                        M[s].st(dl, op.dst_row + w0 + k, lane, g0[k] ^ ((g0[k] ^ g1[k]) & m));
+                    }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         const uint32_t *g = (const uint32_t *)y[s] + op.src_row;  // g(y, 0) words; g(y, 1) at + nwo

@@ -24,7 +24,12 @@ namespace qpd {
 // The root's f and g tables as bytes in LDS once per block (stage_tab): an
 // element's 8-bit index addresses all three results (f, g with u = 0 at +0,
 // u = 1 at +256) -- one field extract and three ds_read_u8 per element.
-template <class In>
+// LO (rows in lookup order, QPD_ROW_BYTEIDX: FastHostPlan::row_lo): each of the three
+// rows as S[1] in that order -- word w holds child elements 4w .. 4w+3 in the high
+// nibbles and N/4 + 4w .. in the low ones, so the thread of word w reads the channel's
+// four runs of four symbols at 4w, N/4 + 4w, N/2 + 4w, 3N/4 + 4w: the same lookups and
+// bytes, one store per row as before.
+template <class In, bool LO = false>
 __global__ __launch_bounds__(256) void root_pre_kernel(FastPlan P, const In *__restrict__ in, int64_t B,
                                                        uint32_t *__restrict__ pre) {
     __shared__ __attribute__((aligned(16))) uint8_t tf[256], tg[512];
@@ -42,17 +47,20 @@ __global__ __launch_bounds__(256) void root_pre_kernel(FastPlan P, const In *__r
         const int64_t f = t >> wsh;
         const int w = (int)(t & ((1 << wsh) - 1));
         const In *y = in + (f << P.n);
-        const uint32_t a = chan_word8(y, 8 * w, P.in_vec, P.v, P.err);
-        const uint32_t b = chan_word8(y, half + 8 * w, P.in_vec, P.v, P.err);
+        const int quarter = P.N >> 2;
+        const uint32_t a = LO ? chan_word44(y, 4 * w, quarter + 4 * w, P.in_vec, P.v, P.err) : chan_word8(y, 8 * w, P.in_vec, P.v, P.err);
+        const uint32_t b = LO ? chan_word44(y, half + 4 * w, half + quarter + 4 * w, P.in_vec, P.v, P.err)
+                              : chan_word8(y, half + 8 * w, P.in_vec, P.v, P.err);
         const uint32_t X = ((a << 4) & 0xF0F0F0F0u) | (b & 0x0F0F0F0Fu);  // byte j: index of element 2j
         const uint32_t Y = (a & 0xF0F0F0F0u) | ((b >> 4) & 0x0F0F0F0Fu);  // ... of element 2j + 1
         uint32_t fw = 0, g0 = 0, g1 = 0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const uint32_t idx = __builtin_amdgcn_ubfe((k & 1) ? Y : X, 8 * (k >> 1), 8);
-            fw |= (uint32_t)tf[idx] << (4 * k);
-            g0 |= (uint32_t)tg[idx] << (4 * k);
-            g1 |= (uint32_t)tg[256 + idx] << (4 * k);
+            const int at = 4 * (LO ? il_nib<8>(k) : k);  // (LO: lookup k is child element 4w + k / N/4 + 4w + k - 4)
+            fw |= (uint32_t)tf[idx] << at;
+            g0 |= (uint32_t)tg[idx] << at;
+            g1 |= (uint32_t)tg[256 + idx] << at;
         }
         if (t0 < total) {
             uint32_t *row = pre + (f << (P.n - 2));

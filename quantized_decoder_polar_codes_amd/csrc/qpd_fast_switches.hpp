@@ -77,6 +77,20 @@
 #ifndef QPD_BOT3_BYTEIDX
 #define QPD_BOT3_BYTEIDX 1
 #endif
+// QPD_ROW_BYTEIDX: the plain kinds (SC-LUT, SCL-LUT, CA-SCL-LUT; every set count,
+// W16, the prefix kernels) keep every S row of M >= 8 symbols in lookup order --
+// word w holds elements 4w .. 4w+3 in the high nibbles of its bytes and elements
+// 4w + M/2 .. in the low ones (M = 8: BOT3's W3 order) -- so the bytes of a stored
+// word are the table indices a * 16 + b of the f / g op below it as they lie:
+// lut_lds / lut_vec build no index words, an unfolded BOT3 no nib_interleave8
+// (DESIGN.md section 3.2).  The plan compiler marks such plans (MF_LO,
+// FastHostPlan::row_lo) and the pre-pass producers follow it.  FastSCL-LUT and
+// FastSC-LUT keep the element order whatever the value: their special nodes and
+// BOTX read symbols by nibble position.  Static count and A/B:
+// profiles/AB_RECORDS.md, `row_byteidx_ab.jsonl`.
+#ifndef QPD_ROW_BYTEIDX
+#define QPD_ROW_BYTEIDX 1
+#endif
 #ifndef QPD_SPEC_ROT
 #define QPD_SPEC_ROT 1  // special ops: one code copy, the sets rotated through slot 0 (else unrolled)
 #endif

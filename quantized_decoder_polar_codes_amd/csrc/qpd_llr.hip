@@ -38,7 +38,8 @@
 
 namespace qpd {
 
-enum LlrOut { LLR_PRE = 0, LLR_I32 = 1, LLR_U8 = 2 };
+// LLR_PRE_LO: the pre-pass row in lookup order (FastHostPlan::row_lo; root_pre_kernel<In, true>)
+enum LlrOut { LLR_PRE = 0, LLR_I32 = 1, LLR_U8 = 2, LLR_PRE_LO = 3 };
 
 struct LlrFront {
     LlrQuant Q;
@@ -82,9 +83,13 @@ __device__ __forceinline__ uint32_t llr_sym(double x, const LlrQuant &Q, const d
     return s < 0 ? 0u : (uint32_t)s;
 }
 
-template <class T, int OUT, bool COOP>
+template <class T, int OUT_, bool COOP>
 __global__ __launch_bounds__(256) void llr_front_kernel(LlrFront C, const T *__restrict__ in, int64_t B,
                                                         void *__restrict__ out) {
+    // LO: word w's eight `a` symbols are the runs at 4w and N/4 + 4w of the row's first half, its `b`
+    // symbols the same of the second half, and lookup k lands at nibble il_nib<8>(k)
+    constexpr bool LO = OUT_ == LLR_PRE_LO;
+    constexpr int OUT = LO ? (int)LLR_PRE : OUT_;
     constexpr int EPL = 16 / (int)sizeof(T);  // LLRs per 16-byte load: 2 or 4
     __shared__ __attribute__((aligned(16))) double E[kLlrMaxEdges + 1];
     __shared__ __attribute__((aligned(16))) uint8_t lut[kLlrMaxEdges - 1];
@@ -124,6 +129,10 @@ __global__ __launch_bounds__(256) void llr_front_kernel(LlrFront C, const T *__r
                     const int64_t tu = base + u < total ? base + u : total - 1;
                     const T *src = in + ((tu >> wsh) << C.n) + (i / LPW) * half + 8 * (int)(tu & ((1 << wsh) - 1)) +
                                    (p % LPW) * EPL;
+                    if constexpr (LO) {  // symbols at .. at + EPL - 1 of word wu: the run at 4 wu, or at N/4 + 4 wu
+                        const int wu = (int)(tu & ((1 << wsh) - 1)), at = (p % LPW) * EPL;
+                        src = in + ((tu >> wsh) << C.n) + (i / LPW) * half + 4 * wu + (at < 4 ? at : (half >> 1) + at - 4);
+                    }
                     llr_load<T, EPL>(src, vec, x[i]);
                 }
 #pragma unroll
@@ -143,12 +152,13 @@ __global__ __launch_bounds__(256) void llr_front_kernel(LlrFront C, const T *__r
                 b = nib_pack4(b8.x) | (nib_pack4(b8.y) << 16);
                 __syncthreads();  // sy is rewritten by the next 256 words
             } else {
-                const T *y = in + (f << C.n) + 8 * w;
+                const T *y = in + (f << C.n) + (LO ? 4 : 8) * w;
                 double x[2][8 / EPL][EPL];
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
 #pragma unroll
-                    for (int i = 0; i < 8 / EPL; ++i) llr_load<T, EPL>(y + h * half + i * EPL, vec, x[h][i]);
+                    for (int i = 0; i < 8 / EPL; ++i)
+                        llr_load<T, EPL>(y + h * half + (LO && i * EPL >= 4 ? (half >> 1) + i * EPL - 4 : i * EPL), vec, x[h][i]);
 #pragma unroll
                 for (int i = 0; i < 8 / EPL; ++i)
 #pragma unroll
@@ -164,9 +174,10 @@ __global__ __launch_bounds__(256) void llr_front_kernel(LlrFront C, const T *__r
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const uint32_t idx = __builtin_amdgcn_ubfe((k & 1) ? Y : X, 8 * (k >> 1), 8);
-                fw |= (uint32_t)tf[idx] << (4 * k);
-                g0 |= (uint32_t)tg[idx] << (4 * k);
-                g1 |= (uint32_t)tg[256 + idx] << (4 * k);
+                const int nb = 4 * (LO ? il_nib<8>(k) : k);
+                fw |= (uint32_t)tf[idx] << nb;
+                g0 |= (uint32_t)tg[idx] << nb;
+                g1 |= (uint32_t)tg[256 + idx] << nb;
             }
             if (t0 < total) {
                 uint32_t *row = pre + (f << (C.n - 2));

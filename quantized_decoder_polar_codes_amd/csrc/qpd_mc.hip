@@ -59,13 +59,14 @@ namespace qpd {
 // changes this kernel's register allocation -- profiles/AB_RECORDS.md.)
 // What the generator writes per frame: int32 symbols, the root pre-pass row,
 // the float64 LLRs, or the reconstruction values of the LLRs' symbols.
-enum McMode { MC_SYM = 0, MC_PRE = 1, MC_LLR = 2, MC_LLR_REC = 3 };
+// MC_PRE_LO: the pre-pass row in lookup order (FastHostPlan::row_lo; root_pre_kernel<In, true>)
+enum McMode { MC_SYM = 0, MC_PRE = 1, MC_LLR = 2, MC_LLR_REC = 3, MC_PRE_LO = 4 };
 template <int MODE>
 __global__ __launch_bounds__(64, QPD_MC_WPE) void mc_frames_kernel(McChannel C, int64_t frame0, int64_t B,
                                                        uint8_t *__restrict__ msg_out, int32_t *__restrict__ sym_out) {
 #pragma clang fp contract(off)
     extern __shared__ uint32_t lds_mc[];
-    constexpr bool PRE = MODE == MC_PRE;
+    constexpr bool PRE = MODE == MC_PRE || MODE == MC_PRE_LO, LO = MODE == MC_PRE_LO;
     constexpr bool LLR = MODE == MC_LLR || MODE == MC_LLR_REC;  // sym_out holds doubles, N per frame
     constexpr bool QUANT = MODE != MC_LLR;                      // the channel quantizer runs
     // PRE: sym_out holds pre-pass rows (N/4 dwords per frame), see McChannel
@@ -205,12 +206,18 @@ __global__ __launch_bounds__(64, QPD_MC_WPE) void mc_frames_kernel(McChannel C, 
                 const int w = min(w0 + t, nwh - 1);
                 uint32_t a = 0, b = 0;
                 for (int i = 0; i < 8; ++i) {
+                    if constexpr (LO) {  // the runs of four symbols at 4w and N/4 + 4w of each half (root_pre_kernel)
+                        const int e = 4 * w + (i < 4 ? i : (N >> 2) + i - 4);
+                        a |= (uint32_t)sy[e] << (4 * i);
+                        b |= (uint32_t)sy[(N >> 1) + e] << (4 * i);
+                        continue;
+                    }
                     a |= (uint32_t)sy[8 * w + i] << (4 * i);
                     b |= (uint32_t)sy[(N >> 1) + 8 * w + i] << (4 * i);
                 }
-                const uint32_t fw = lut_vec<8>(Tf, a, b, 0u);
-                const uint32_t g0 = lut_vec<8>(Tg, a, b, 0u);
-                const uint32_t g1 = lut_vec<8>(Tg, a, b, 0xFFu);
+                const uint32_t fw = lut_vec<8, LO>(Tf, a, b, 0u);
+                const uint32_t g0 = lut_vec<8, LO>(Tg, a, b, 0u);
+                const uint32_t g1 = lut_vec<8, LO>(Tg, a, b, 0xFFu);
                 if (w0 + t < nwh) {
                     row[w] = fw;
                     row[nwh + w] = g0;
@@ -282,7 +289,7 @@ inline size_t mc_lds_bytes(int N, int K, int mode) {
     const size_t tables = mode == MC_LLR ? 0
                                          : (kMcMaxEdges + 1) * sizeof(double) + kMcMaxEdges * sizeof(int32_t) +
                                                (mode == MC_LLR_REC ? (kMcMaxEdges - 1) * sizeof(double) : 0);
-    return tables + 4 * (((N + 31) >> 5) + ((K + 31) >> 5) + 2) + (mode == MC_PRE ? (size_t)N : 0);
+    return tables + 4 * (((N + 31) >> 5) + ((K + 31) >> 5) + 2) + (mode == MC_PRE || mode == MC_PRE_LO ? (size_t)N : 0);
 }
 
 }  // namespace qpd

@@ -4,6 +4,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "qpd_fast_switches.hpp"
 #include "qpd_types.hpp"
 
 namespace qpd {
@@ -52,6 +53,9 @@ enum MopFlag : int32_t {
                             //   depth n-4 parent's 16 (src = S[n-4], the parent's table at tab): no F op
     MF_SGG = 268435456,     //   ... as g of them, u = the left sibling's U[n-3] at u_row (sh_u): no G op
     MF_SCOMB = 536870912,   //   ... and runs the parent's combine with that U[n-3] (dst = the parent's): no COMB
+    MF_LO = 1073741824,     // F / G / BOT3 of a plan whose S rows of >= 8 symbols are in lookup order
+                            //   (QPD_ROW_BYTEIDX, FastHostPlan::row_lo): the op's source (a row or pre-pass row of
+                            //   >= 8 symbols) is read, its destination (>= 8 symbols) written in that order
 };
 
 struct MOp {

@@ -120,6 +120,7 @@ struct FastHostPlan {
     bool r1l = false;  // an R1 node needs r1_large (the R1L instantiation)
     bool pw1 = false;  // one pointer word per path (compact_pointer_fields)
     bool pre = false;  // root pre-pass
+    bool row_lo = false;  // S rows of >= 8 symbols and the pre-pass rows in lookup order (QPD_ROW_BYTEIDX; MF_LO)
     int64_t pre_chunk = 0;  // frames per pre-pass chunk
     FastLayout layout;                  // the final layout and the row slots it keeps
     bool use[3][qpd::kMaxDepth + 1];    //   (slot 0 R, 1 S, 2 U; per depth): see make_owner
@@ -1066,6 +1067,14 @@ inline int plan_fast(const qpd_config &c, int n, int L, const Schedule &s, const
     P.pfx_sets = std::min(P.sets, 2);
     if (sw.pfx_sets) P.pfx_sets = std::min(P.pfx_sets, sw.pfx_sets);
     const std::vector<std::vector<qpd::MOp> *> lists = {&mops, &P.pfx[0], &P.pfx[1], &P.pfx[2]};
+    // Rows in lookup order (QPD_ROW_BYTEIDX, qpd_fast_switches.hpp): the plain kinds, whose S rows of
+    // >= 8 symbols only f / g ops and BOT3s read.  Row sizes, slots and pointers are what they were;
+    // only the order of a row's nibbles changes, which every op of the plan then agrees on.
+    P.row_lo = QPD_ROW_BYTEIDX != 0 && (c.kind == QPD_SC_LUT || c.kind == QPD_SCL_LUT);
+    if (P.row_lo)
+        for (auto *l : lists)
+            for (qpd::MOp &m : *l)
+                if (m.type == qpd::OP_F || m.type == qpd::OP_G || m.type == qpd::OP_BOT3) m.flags |= qpd::MF_LO;
     for (auto *l : lists) {
         // folded descents: the list kernels with two frame sets (ff_op)
         if (list_kind && !sw.no_ff && (l == &mops ? P.sets : P.pfx_sets) == 2) fuse_descent(*l);
