@@ -332,6 +332,75 @@ int qpd_decode_list_host(qpd_decoder *dec, const void *h_in, int32_t in_type, in
                          const qpd_list_args *ls);
 
 /*
+ * Mask search: one list decode against a whole set of CRC masks -- what a PDCCH
+ * receiver does for every candidate frame: it holds several RNTIs and asks which of
+ * them, if any, the frame is addressed to, and on which list path.  Instead of one
+ * qpd_decode_status per mask, or qpd_decode_list's L * K candidate bytes and a CRC pass
+ * by the caller, every candidate is reported as one word, its CRC syndrome, and the set
+ * is compared against it in the decode's tail.  CRC-aided kinds only, on every engine.
+ *
+ * Candidates are in qpd_decode_list's order: r = the path's position in argsort(PML)
+ * (stable, L <= 16).  chk = the number of compared check bits: K - A for the LUT kinds,
+ * crc_n for QPD_CASCL_FLOAT (the compare of qpd_config.A above).
+ *   cand_syndrome[f][r]  bit chk-1-j = check bit j of path r (its decision at
+ *                        information position A + j) XOR bit crc_n-1-j of the CRC
+ *                        register after the path's A message bits, j < chk: the
+ *                        compare of qpd_decode_status with no mask, collected instead
+ *                        of ANDed.  0: the path passes the plain CRC.  Or NULL.
+ *   cand_metric[f][r]    that path's own final PML double (qpd_list_args.cand_metric);
+ *                        or NULL.
+ *   crc_masks            n_masks rows of crc_mask_bits entries 0 / 1, each row placed
+ *                        as qpd_status_args.crc_mask: row i has the register value
+ *                        M_i = sum of crc_masks[i][l] << (crc_mask_bits - 1 - l).  Mask
+ *                        i passes candidate r iff
+ *                            cand_syndrome[f][r] == M_i >> (crc_n - chk)
+ *                        -- exactly qpd_decode_status's compare under that mask.  With
+ *                        chk == crc_n this is plain equality: a 16-bit RNTI under
+ *                        which a word was sent is the syndrome itself (an unknown RNTI
+ *                        is read off cand_syndrome when it is below 2^16).
+ *   The output path is the lowest r that any mask passes; hit_mask[f] the lowest i that
+ *   passes it (duplicate masks resolve to the first), hit_rank[f] = r.  No mask passes
+ *   any candidate: hit_mask[f] = -1, hit_rank[f] = 0, the output path is the
+ *   best-metric path (qpd_decode_status's "none did").  d_out receives the output
+ *   path's A bits, metric[f] its own PML.  Each of the three and d_out may be NULL.
+ * With n_masks == 1 the call is qpd_decode_status with that mask, bit for bit: d_out
+ * and metric are its, crc_pass == (hit_mask >= 0), hit_rank == qpd_decode_list's chosen.
+ * n_masks == 0: the syndromes and metrics alone; without a mask set there is no defined
+ * output path, so d_out, hit_mask, hit_rank and metric must be NULL (QPD_E_INVALID).
+ * crc_masks is always a host pointer, read before the call returns.  The set is kept in
+ * a device buffer of the decoder's.  A call whose set equals the resident one enqueues
+ * its launches and returns, as qpd_decode_list does; a call with another set first
+ * uploads it on the decoder's own stream, behind the decoder's previous work (which may
+ * still read the old set), and BLOCKS the host until that upload is done -- so a
+ * receiver that alternates sets on one handle synchronizes once per call (use one
+ * decoder per set), and such a call cannot be captured into a graph.  The outputs are
+ * device pointers in qpd_decode_search, host pointers in qpd_decode_search_host.
+ * Frames >= B are never written; a frame with an error flag (qpd_check_input_error)
+ * keeps what the caller left.  in_type, stream ordering, the per-handle lock, the error
+ * word, qpd_info.last_engine and the host variant's host_max_frames dispatch: as
+ * qpd_decode_list / _host.
+ * Refused before any launch: a kind without CRC, the SC / FastSC kinds, a mask entry
+ * above 1, crc_mask_bits outside [0, crc_n], n_masks outside [0, QPD_MAX_SEARCH_MASKS],
+ * crc_masks NULL with n_masks * crc_mask_bits > 0, an in_type that does not fit
+ * (QPD_E_INVALID); L = 1 and L > 16 (QPD_E_UNSUPPORTED, as qpd_decode_list).
+ */
+#define QPD_MAX_SEARCH_MASKS 256
+typedef struct qpd_search_args {
+    const uint8_t *crc_masks;   /* host, [n_masks][crc_mask_bits] of 0/1 (each row as qpd_status_args.crc_mask) */
+    int32_t n_masks;            /* 0..QPD_MAX_SEARCH_MASKS                                                      */
+    int32_t crc_mask_bits;      /* 0..crc_n, one width for the whole set                                        */
+    uint32_t *cand_syndrome;    /* [B][L] or NULL                                                               */
+    double   *cand_metric;      /* [B][L] or NULL                                                               */
+    int32_t  *hit_mask;         /* [B] or NULL: index of the mask that passed, -1: none                         */
+    int32_t  *hit_rank;         /* [B] or NULL: rank r of the output path                                       */
+    double   *metric;           /* [B] or NULL: the output path's metric                                        */
+} qpd_search_args;
+int qpd_decode_search(qpd_decoder *dec, const void *d_in, int32_t in_type, int64_t B, uint8_t *d_out,
+                      const qpd_search_args *sr, void *stream);
+int qpd_decode_search_host(qpd_decoder *dec, const void *h_in, int32_t in_type, int64_t B, uint8_t *h_out,
+                           const qpd_search_args *sr);
+
+/*
  * Blind-detection metric (D-metric): the cheap half of PDCCH blind detection, one
  * double per candidate frame, by which a receiver ranks its candidates before it
  * runs the list decode above on the best few.  The counterpart of the reference's

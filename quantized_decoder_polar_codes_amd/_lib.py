@@ -53,6 +53,8 @@ EXPORTED = (
     "qpd_decode_status_host",
     "qpd_decode_list",
     "qpd_decode_list_host",
+    "qpd_decode_search",
+    "qpd_decode_search_host",
     "qpd_dmetric",
     "qpd_dmetric_host",
     "qpd_encode",
@@ -139,6 +141,22 @@ class QpdListArgs(ctypes.Structure):
         ("cand_pass", _P),
         ("chosen", _P),
     ]
+
+
+class QpdSearchArgs(ctypes.Structure):
+    _fields_ = [
+        ("crc_masks", _P),
+        ("n_masks", _i32),
+        ("crc_mask_bits", _i32),
+        ("cand_syndrome", _P),
+        ("cand_metric", _P),
+        ("hit_mask", _P),
+        ("hit_rank", _P),
+        ("metric", _P),
+    ]
+
+
+QPD_MAX_SEARCH_MASKS = 256
 
 
 class QpdTxArgs(ctypes.Structure):
@@ -260,6 +278,11 @@ def load():
         L.qpd_decode_list.restype = ctypes.c_int
         L.qpd_decode_list_host.argtypes = [_P, _P, _i32, _i64, _P, ctypes.POINTER(QpdListArgs)]
         L.qpd_decode_list_host.restype = ctypes.c_int
+    if not os.environ.get("QPD_LIB") or hasattr(L, "qpd_decode_search"):
+        L.qpd_decode_search.argtypes = [_P, _P, _i32, _i64, _P, ctypes.POINTER(QpdSearchArgs), _P]
+        L.qpd_decode_search.restype = ctypes.c_int
+        L.qpd_decode_search_host.argtypes = [_P, _P, _i32, _i64, _P, ctypes.POINTER(QpdSearchArgs)]
+        L.qpd_decode_search_host.restype = ctypes.c_int
     if not os.environ.get("QPD_LIB") or hasattr(L, "qpd_dmetric"):
         L.qpd_dmetric.argtypes = [_P, _P, _i64, _P, _P, _P]
         L.qpd_dmetric.restype = ctypes.c_int

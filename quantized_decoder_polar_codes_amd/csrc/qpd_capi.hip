@@ -128,6 +128,66 @@ int list_host(qpd_decoder *d, Eng *eng, const In *h_in, int32_t in_type, int64_t
     });
 }
 
+// The checks of both search entry points: the request (qpd_search.hpp), then the decode's
+// own, with the bits optional.
+int check_search_call(const qpd_decoder *d, int32_t in_type, const qpd_search_args *sa, const char *suffix, int64_t B,
+                      const void *in, const void *out, qpd_search::Req *rq, bool *run) {
+    *run = false;
+    if (!d) return fail(QPD_E_INVALID, "null decoder");
+    std::string err;
+    const int rc = qpd_search::check(d->pub_kind, d->L, d->K, d->ca_A, d->crc_n, in_type, sa, out != nullptr, rq, err);
+    if (rc) return fail(rc, err);
+    return check_decode_args(d, in_type != QPD_IN_F64, suffix, B, in, d, run);  // (no required output)
+}
+
+// One device-buffer search decode (caller: lock held, stream ordered): as decode_list_typed.
+int decode_search_typed(qpd_decoder *d, const void *d_in, int32_t in_type, int64_t B, uint8_t *d_out,
+                        const qpd_search::Req &rq, hipStream_t st) {
+    uint8_t *base = d_out;
+    if (!base) {  // a launch finds its first frame from where it would write its bits (search_at)
+        const int rc = ensure(d->ls_out, d->ls_out_bytes, (size_t)B * d->out_bits);
+        if (rc) return rc;
+        base = (uint8_t *)d->ls_out.p;
+    }
+    SearchScope sc(d, rq, base);
+    if (sc.rc) return sc.rc;
+    return decode_typed(d, d_in, in_type, B, base, st);
+}
+
+template <class Eng, class In>
+int search_host(qpd_decoder *d, Eng *eng, const In *h_in, int32_t in_type, int64_t B, uint8_t *h_out,
+                const qpd_search::Req &rq) {
+    if (host_engine_takes(d, B)) {
+        std::lock_guard<std::mutex> lk(d->mu);
+        d->last_engine = QPD_RAN_HOST;
+        d->u8_staged = 0;
+        const int32_t flag = qpd_search::host_run(eng, h_in, B, d->N, d->L, d->out_bits, h_out, rq);
+        return flag ? input_error(flag) : QPD_OK;
+    }
+    // the GPU: the results through a device buffer of the handle (metrics, then the 32-bit
+    // outputs: each aligned for its type), copied back on its stream before
+    // host_roundtrip's synchronization
+    const size_t n = (size_t)B * d->L, nb = (size_t)B;
+    return host_roundtrip(d, h_in, B, h_out, [&](const In *in, uint8_t *out, hipStream_t hs) -> int {
+        int rc = ensure(d->h_sr, d->h_sr_bytes, n * 8 + nb * 8 + n * 4 + nb * 8);
+        if (rc) return rc;
+        char *base = (char *)d->h_sr.p;
+        qpd_search::Req dev = rq;
+        if (rq.cand_metric) dev.cand_metric = (double *)base;
+        if (rq.metric) dev.metric = (double *)(base + n * 8);
+        if (rq.syndrome) dev.syndrome = (uint32_t *)(base + n * 8 + nb * 8);
+        if (rq.hit_mask) dev.hit_mask = (int32_t *)(base + n * 8 + nb * 8 + n * 4);
+        if (rq.hit_rank) dev.hit_rank = (int32_t *)(base + n * 8 + nb * 8 + n * 4 + nb * 4);
+        if ((rc = decode_search_typed(d, in, in_type, B, h_out ? out : nullptr, dev, hs))) return rc;
+        if (rq.cand_metric) QPD_HIP(hipMemcpyAsync(rq.cand_metric, dev.cand_metric, n * 8, hipMemcpyDeviceToHost, hs));
+        if (rq.metric) QPD_HIP(hipMemcpyAsync(rq.metric, dev.metric, nb * 8, hipMemcpyDeviceToHost, hs));
+        if (rq.syndrome) QPD_HIP(hipMemcpyAsync(rq.syndrome, dev.syndrome, n * 4, hipMemcpyDeviceToHost, hs));
+        if (rq.hit_mask) QPD_HIP(hipMemcpyAsync(rq.hit_mask, dev.hit_mask, nb * 4, hipMemcpyDeviceToHost, hs));
+        if (rq.hit_rank) QPD_HIP(hipMemcpyAsync(rq.hit_rank, dev.hit_rank, nb * 4, hipMemcpyDeviceToHost, hs));
+        return QPD_OK;
+    });
+}
+
 // The checks of both D-metric entry points (qpd_dmetric.hpp), before any launch.
 // *run = false where there is nothing to compute (a refusal, or an empty batch).
 int check_dmetric_call(const qpd_decoder *d, int64_t B, const void *in, const void *metric, bool *run) {
@@ -283,6 +343,29 @@ int qpd_decode_list_host(qpd_decoder *d, const void *h_in, int32_t in_type, int6
         case QPD_IN_I32: return list_host(d, d->heng_lut.get(), (const int32_t *)h_in, in_type, B, h_out, rq);
         case QPD_IN_U8: return list_host(d, d->heng_lut.get(), (const uint8_t *)h_in, in_type, B, h_out, rq);
         default: return list_host(d, d->heng_f64.get(), (const double *)h_in, in_type, B, h_out, rq);
+    }
+}
+
+int qpd_decode_search(qpd_decoder *d, const void *d_in, int32_t in_type, int64_t B, uint8_t *d_out,
+                      const qpd_search_args *sa, void *stream) {
+    bool run;
+    qpd_search::Req rq;
+    const int rc = check_search_call(d, in_type, sa, "", B, d_in, d_out, &rq, &run);
+    if (!run) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return ordered(d, st, [&]() { return decode_search_typed(d, d_in, in_type, B, d_out, rq, st); });
+}
+
+int qpd_decode_search_host(qpd_decoder *d, const void *h_in, int32_t in_type, int64_t B, uint8_t *h_out,
+                           const qpd_search_args *sa) {
+    bool run;
+    qpd_search::Req rq;
+    const int rc = check_search_call(d, in_type, sa, "_host", B, h_in, h_out, &rq, &run);
+    if (!run) return rc;
+    switch (in_type) {
+        case QPD_IN_I32: return search_host(d, d->heng_lut.get(), (const int32_t *)h_in, in_type, B, h_out, rq);
+        case QPD_IN_U8: return search_host(d, d->heng_lut.get(), (const uint8_t *)h_in, in_type, B, h_out, rq);
+        default: return search_host(d, d->heng_f64.get(), (const double *)h_in, in_type, B, h_out, rq);
     }
 }
 

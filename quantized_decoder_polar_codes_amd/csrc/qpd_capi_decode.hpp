@@ -83,21 +83,56 @@ void list_at(const qpd_decoder *d, const uint8_t *out, Plan &P) {
     P.ls_chosen = rq.chosen ? rq.chosen + f0 : nullptr;
 }
 
+// Likewise the search fields during qpd_decode_search, over the list fields it shares (cand_metric,
+// hit_rank) and the status call's metric.  FS: FastStatus (its sr_* fields) or the generic
+// kernels' DevSearch.
+template <class Plan>
+void search_shared_at(const qpd_decoder *d, int64_t f0, Plan &P) {
+    const qpd_search::Req &rq = d->sr_req;
+    P.crc_mask = 0;
+    P.ls_bits = nullptr;
+    P.ls_pass = nullptr;
+    P.ls_metric = rq.cand_metric ? rq.cand_metric + f0 * d->L : nullptr;
+    P.ls_chosen = rq.hit_rank ? rq.hit_rank + f0 : nullptr;
+    P.st_metric = rq.metric ? rq.metric + f0 : nullptr;
+    P.st_pass = nullptr;
+}
+void search_at(const qpd_decoder *d, const uint8_t *out, qpd::FastStatus &so) {
+    const qpd_search::Req &rq = d->sr_req;
+    const int64_t f0 = (out - d->st_out0) / d->out_bits;
+    search_shared_at(d, f0, so);
+    so.sr_set = (const uint32_t *)d->sr_set.p;
+    so.sr_n = (int32_t)rq.words.size();
+    so.sr_syndrome = rq.syndrome ? rq.syndrome + f0 * d->L : nullptr;
+    so.sr_hit = rq.hit_mask ? rq.hit_mask + f0 : nullptr;
+}
+void search_at(const qpd_decoder *d, const uint8_t *out, qpd::DevPlan &P, qpd::DevSearch &sr) {
+    const qpd_search::Req &rq = d->sr_req;
+    const int64_t f0 = (out - d->st_out0) / d->out_bits;
+    search_shared_at(d, f0, P);
+    sr.set = (const uint32_t *)d->sr_set.p;
+    sr.n = (int32_t)rq.words.size();
+    sr.syndrome = rq.syndrome ? rq.syndrome + f0 * d->L : nullptr;
+    sr.hit = rq.hit_mask ? rq.hit_mask + f0 : nullptr;
+}
+
 // dmetric (qpd_dmetric, a float FastSC decoder): the launch runs the kernel's DM twin, which writes
 // the frames' blind-detection metrics there and takes a NULL out; the plain kernels do not read it.
 template <class In>
 int launch_generic(qpd_decoder *d, const In *in, int64_t B, uint8_t *out, int grid, hipStream_t st,
                    double *dmetric = nullptr) {
     const void *kfn = dmetric            ? qpd::dmetric_kernel()
-                      : d->ls_req.any() ? qpd::generic_list_kernel(d->kind, d->dom, d->L > qpd::kMaxL)
+                      : d->ls_req.any() || d->sr_req.any() ? qpd::generic_list_kernel(d->kind, d->dom, d->L > qpd::kMaxL)
                                         : generic_kernel(d->kind, d->dom, d->L > qpd::kMaxL);
     if (!kfn) return fail(QPD_E_INVALID, "bad kind");
     qpd::DevPlan P = d->plan;
     P.task_base = d->task_base;
     status_at(d, out, P);
     list_at(d, out, P);
+    qpd::DevSearch sr{};
+    if (d->sr_req.any()) search_at(d, out, P, sr);
     const In *in_arg = in;
-    void *args[] = {&P, &in_arg, &B, &out, &dmetric};
+    void *args[] = {&P, &in_arg, &B, &out, &dmetric, &sr};
     const int rc = timed_launch(d, QPD_KC_DECODE, st, [&]() -> int {
         QPD_HIP(hipLaunchKernel(kfn, dim3(grid), dim3(64), args, 0, st));
         QPD_HIP(hipGetLastError());
@@ -115,13 +150,16 @@ int fast_launch(qpd_decoder *d, qpd::FastPlan fp, const int32_t *in, int64_t Bc,
     const int64_t tw = (int64_t)fp.fpw * sets;  // frames per wave task
     // a status call's decode launch runs the plan's ST twin (the plain kernels do not read the status fields)
     // ... and a list call's the LIST twin
-    const bool status = !prefix && d->st_req.any(), list = !prefix && d->ls_req.any();
+    // ... and so does a search call's, with the search fields set
+    const bool search = !prefix && d->sr_req.any();
+    const bool status = !prefix && d->st_req.any(), list = !prefix && (d->ls_req.any() || search);
     const void *kfn = prefix ? prefix_kernel(d->kind, sets, d->pw1)
                              : fast_kernel(d->kind, d->sets, d->l8, d->r1l, d->pw1, d->w16, list ? 2 : status ? 1 : 0);
     if (!kfn) return fail(QPD_E_INVALID, "bad kind");
     qpd::FastStatus so{};
     if (status) status_at(d, out, so);
     if (list) list_at(d, out, so);
+    if (search) search_at(d, out, so);
     const int64_t fgroups = (Bc + tw - 1) / tw;
     int fgrid = (int)std::min<int64_t>(fgroups, d->max_waves);
     if (!QPD_DYN) {
@@ -310,6 +348,41 @@ struct StatusScope {
     }
     ~StatusScope() {
         d->st_req = qpd_stat::Req();
+        d->st_out0 = nullptr;
+    }
+};
+
+// The search request of a call, likewise (the call's d_out, or ls_out when it gave none), and
+// its set made resident: a set that differs from the resident one is uploaded on the
+// decoder's own stream, after the decoder's previous work (which may still read the old
+// set), and waited for, so that every launch of the call, on any stream, finds it.
+struct SearchScope {
+    qpd_decoder *d;
+    int rc = QPD_OK;
+    SearchScope(qpd_decoder *d_, const qpd_search::Req &rq, const uint8_t *out0) : d(d_) {
+        d->sr_req = rq;
+        d->st_out0 = out0;
+        rc = upload_set();
+    }
+    int upload_set() {
+        if (!d->sr_set.p) {
+            QPD_HIP(hipMalloc(&d->sr_set.p, QPD_MAX_SEARCH_MASKS * sizeof(uint32_t)));
+            d->sr_set_host.clear();
+        } else if (d->sr_set_host == d->sr_req.words) {
+            return QPD_OK;
+        }
+        d->sr_set_host.clear();  // (nothing resident, should the upload fail)
+        if (d->sr_req.words.empty()) return QPD_OK;
+        const int orc = order_on(d, d->hs);
+        if (orc) return orc;
+        QPD_HIP(hipMemcpyAsync(d->sr_set.p, d->sr_req.words.data(), d->sr_req.words.size() * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, d->hs));
+        QPD_HIP(hipStreamSynchronize(d->hs));
+        d->sr_set_host = d->sr_req.words;
+        return QPD_OK;
+    }
+    ~SearchScope() {
+        d->sr_req = qpd_search::Req();
         d->st_out0 = nullptr;
     }
 };

@@ -231,14 +231,24 @@ __device__ __forceinline__ int stable_rank(double pm, int gl, int gbase, int L) 
 // CASCLWithRNTI.cpp:222-224; 0: none).  *passed: a path passed the compare -- the
 // output path is the first that did (the reference's isPass).  own (list output,
 // else NULL): this lane's own compare.
-template <class WordFn>
+// syn (mask search, qpd_decode_search; else NULL): this lane's CRC syndrome -- the compare
+// with no mask, collected instead of ANDed: bit chk-1-j = check bit j XOR register bit
+// crc_n-1-j.  set (mask search; else NULL): nset words, wave-uniform, each a mask's
+// register value >> (crc_n - chk); a path then passes iff its syndrome equals one of them
+// (crc_mask is not read), *hit = the lowest such index, -1: none.  SR: the search's
+// out-parameters are read at all -- a template switch, so that every other caller
+// compiles to the instructions it had before the search existed.
+template <bool SR = false, class WordFn>
 __device__ __forceinline__ int ca_winner_ranked(int rank, int gl, int gbase, int L, int N, const uint32_t *info_mask,
                                                 int A, int chk, int crc_n, uint32_t crc_q, WordFn word,
-                                                uint32_t crc_mask, bool *passed, bool *own = nullptr) {
+                                                uint32_t crc_mask, bool *passed, bool *own = nullptr,
+                                                uint32_t *syn = nullptr, const uint32_t *set = nullptr, int nset = 0,
+                                                int *hit = nullptr) {
     const int K = A + chk;
     const uint32_t top = 1u << (crc_n - 1);
     const uint32_t mask = (top << 1) - 1u;  // crc_n = 32: 0 - 1 = all ones
     uint32_t r = 0;
+    [[maybe_unused]] uint32_t sy = 0;
     bool pass = true;
     int t = 0;
     const int nw = (N + 31) >> 5;
@@ -255,8 +265,18 @@ __device__ __forceinline__ int ca_winner_ranked(int rank, int gl, int gbase, int
                 r = ((r << 1) & mask) ^ (crc_q & (0u - fb));
             } else {
                 pass = pass && bit == (((r ^ crc_mask) >> (crc_n - 1 - (t - A))) & 1u);
+                if constexpr (SR) sy |= (bit ^ ((r >> (crc_n - 1 - (t - A))) & 1u)) << (chk - 1 - (t - A));
             }
             ++t;
+        }
+    }
+    if constexpr (SR) {
+        *syn = sy;
+        if (set) {  // the set compare: one scalar word per mask against every lane's syndrome
+            int h = -1;
+            for (int i = nset - 1; i >= 0; --i) h = set[i] == sy ? i : h;
+            pass = h >= 0;
+            *hit = h;
         }
     }
     const int key = gl < L ? (pass ? rank : kMaxLWide + rank) : 2 * kMaxLWide;

@@ -20,6 +20,7 @@
 #include "qpd_host.hpp"
 #include "qpd_status.hpp"
 #include "qpd_list.hpp"
+#include "qpd_search.hpp"
 #include "qpd_tx.hpp"
 
 namespace {
@@ -175,6 +176,14 @@ struct qpd_decoder {
     size_t ls_out_bytes = 0;
     DeviceBuf h_ls;  // qpd_decode_list_host's device outputs: bits, metrics, flags, chosen
     size_t h_ls_bytes = 0;
+    // qpd_decode_search, likewise; the mask set's words in a device buffer of the handle
+    // (QPD_MAX_SEARCH_MASKS words), uploaded on the handle's own stream when it changes
+    // (SearchScope, qpd_capi_decode.hpp); sr_set_host: what is resident
+    qpd_search::Req sr_req;
+    DeviceBuf sr_set;
+    std::vector<uint32_t> sr_set_host;
+    DeviceBuf h_sr;  // qpd_decode_search_host's device outputs
+    size_t h_sr_bytes = 0;
     // qpd_profile: HIP events around every launch, per kernel class
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[QPD_KC_COUNT];

@@ -512,10 +512,15 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
                 // writes its own metric and CRC verdict at its rank.
                 const int rank = stable_rank(stv[s].pm, gl, gbase, L);
                 bool passed = false, own = false;
-                int best = 0;
+                int best = 0, hit = -1;
+                uint32_t syn = 0;
+                // a mask search (qpd_decode_search; wave-uniform): the winner by the set compare
+                // on each lane's syndrome, no candidate bits
+                const bool search = SO.sr_set != nullptr;
                 if (P.crc_n > 0)
-                    best = ca_winner_ranked(rank, gl, gbase, L, N, P.info_mask, P.ca_A, P.K - P.ca_A, P.crc_n, P.crc_q,
-                                            [&](int w) { return M.ld(rl, r0 + w, lane); }, SO.crc_mask, &passed, &own);
+                    best = ca_winner_ranked<true>(rank, gl, gbase, L, N, P.info_mask, P.ca_A, P.K - P.ca_A, P.crc_n, P.crc_q,
+                                            [&](int w) { return M.ld(rl, r0 + w, lane); }, SO.crc_mask, &passed, &own,
+                                            &syn, SO.sr_set, SO.sr_n, &hit);
                 const int64_t frame = (task * NS + s) * fpw + lane / gs;
                 const bool live = frame < B;
                 auto bit = [&](int pos, int src) { return (M.ldv(rl, r0 + (pos >> 5), src) >> (pos & 31)) & 1u; };
@@ -545,7 +550,7 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
                     }
                 };
                 const bool dword_ls = (P.K & 3) == 0 && ((uintptr_t)SO.ls_bits & 3) == 0;
-                for (int r = 0; r < L; ++r) {
+                for (int r = 0; r < L && !search; ++r) {
                     // the group's lane of rank r (one per group; the ballot by the whole wave)
                     const uint64_t m = __ballot(gl < L && rank == r) >> gbase;
                     const int src = gbase + (__builtin_ctzll(m | (1ull << 63)) & (gs - 1));
@@ -553,6 +558,15 @@ __global__ __launch_bounds__(64, NS == 3 ? QPD_WPE3
                     if (live) gather(SO.ls_bits + (frame * L + r) * (int64_t)P.K, P.K, src, dword_ls);
                 }
                 const int crank = lane_read(rank, gbase + best);
+                if (search) {  // the output path's hit and own metric, by the group's first lane
+                    const int whit = lane_read(hit, gbase + best);
+                    const double wpm = shfld(stv[s].pm, gbase + best);
+                    if (live && gl < L && SO.sr_syndrome) SO.sr_syndrome[frame * L + rank] = syn;
+                    if (live && gl == 0) {
+                        if (SO.sr_hit) SO.sr_hit[frame] = whit;
+                        if (SO.st_metric) SO.st_metric[frame] = wpm;
+                    }
+                }
                 if (live) {
                     if (gl < L) {
                         if (SO.ls_metric) SO.ls_metric[frame * L + rank] = stv[s].pm;

@@ -64,6 +64,14 @@ struct FastStatus {
     double *ls_metric;   // [B][L] or NULL
     uint8_t *ls_pass;    // [B][L] or NULL: the path's own CRC compare
     int32_t *ls_chosen;  // [B] or NULL: the candidate whose bits `out` receives
+    // Mask search (qpd_decode_search), read by the LIST instantiations' tail alone, again at
+    // the end.  sr_set != NULL: a search call -- ls_bits is NULL (no candidate bits are
+    // gathered), ls_metric / ls_chosen are the call's cand_metric / hit_rank, st_metric its
+    // metric, and the output path is chosen by the set compare (ca_winner_ranked).
+    const uint32_t *sr_set;  // [sr_n] the masks' register values >> (crc_n - chk), in a buffer of the decoder's
+    int32_t sr_n;
+    uint32_t *sr_syndrome;   // [B][L] or NULL: every path's CRC syndrome at its rank
+    int32_t *sr_hit;         // [B] or NULL: the lowest mask index that passes the output path, -1: none
 };
 
 // Row access in either space.  `in_lds` is wave-uniform.  The global slab is

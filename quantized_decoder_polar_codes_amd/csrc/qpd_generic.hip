@@ -87,6 +87,19 @@ struct DevPlan {
     int32_t *ls_chosen;  // [B] or NULL: the candidate whose bits `out` receives
 };
 
+// Mask search (qpd_decode_search), per launch: the decode kernels' last argument, read by the LS
+// instantiations alone (zeros in every other call) -- not part of DevPlan, the first argument, so
+// that no instantiation's other arguments move.  set != NULL: a search call -- P.ls_bits is NULL
+// (no candidate bits are gathered), P.ls_metric / P.ls_chosen are the call's cand_metric /
+// hit_rank, P.st_metric its metric, and the output path is chosen by the set compare
+// (ca_winner_ranked).
+struct DevSearch {
+    const uint32_t *set;  // [n] the masks' register values >> (crc_n - chk), in a buffer of the decoder's
+    int32_t n;
+    uint32_t *syndrome;   // [B][L] or NULL: every path's CRC syndrome at its rank
+    int32_t *hit;         // [B] or NULL: the lowest mask index that passes the output path, -1: none
+};
+
 __device__ __forceinline__ double vcl_at(const DevPlan &P, int row, int pos, int sym) {
     return P.vcl[((size_t)row * P.N + pos) * P.v + sym];
 }
@@ -371,7 +384,7 @@ __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
                                                             const std::conditional_t<DOM == DOM_LUT, int32_t, double>
                                                                 *__restrict__ in,
                                                             int64_t B, uint8_t *__restrict__ out,
-                                                            double *__restrict__ dmetric) {
+                                                            double *__restrict__ dmetric, DevSearch SR) {
     static_assert(!DM || (KIND == K_FASTSC_LUT && DOM == DOM_FLOAT), "the D-metric is float FastSC's");
     static_assert(!LS || KIND == K_SCL_LUT || KIND == K_FASTSCL_LUT, "list output: the list kinds");
     constexpr bool kList = (KIND == K_SCL_LUT || KIND == K_FASTSCL_LUT);
@@ -752,12 +765,15 @@ __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
                 check_keys<DOM>(P, pm, pm);  // the metrics are sorted
                 const int rank = stable_rank(pm, gl, gbase, L);
                 bool passed = false, own = false;
-                int best = 0;
+                int best = 0, hit = -1;
+                uint32_t syn = 0;
+                const bool search = SR.set != nullptr;  // a mask search (qpd_decode_search; wave-uniform)
                 if (P.crc_n > 0)
-                    best = ca_winner_ranked(rank, gl, gbase, L, P.N, P.info_mask, P.ca_A, P.ca_chk, P.crc_n, P.crc_q,
-                                            [&](int w) { return row_ptr(wsc, P.Ro + w)[lane]; }, P.crc_mask, &passed, &own);
+                    best = ca_winner_ranked<true>(rank, gl, gbase, L, P.N, P.info_mask, P.ca_A, P.ca_chk, P.crc_n, P.crc_q,
+                                            [&](int w) { return row_ptr(wsc, P.Ro + w)[lane]; }, P.crc_mask, &passed, &own,
+                                            &syn, SR.set, SR.n, &hit);
                 const uint32_t *rb = row_ptr(wsc, P.Ro);
-                for (int r = 0; r < L; ++r) {
+                for (int r = 0; r < L && !search; ++r) {
                     const uint64_t m = __ballot(gl < L && rank == r) >> gbase;  // (by the whole wave)
                     const int src = gbase + (__builtin_ctzll(m | (1ull << 63)) & (gs - 1));
                     if (r == 0 && P.crc_n == 0) best = src - gbase;  // the first minimum (H6)
@@ -770,6 +786,15 @@ __global__ __launch_bounds__(64) void generic_decode_kernel(DevPlan P,
                     }
                 }
                 const int crank = __shfl(rank, gbase + best);
+                if (search) {  // the output path's hit and own metric, by the group's first lane
+                    const int whit = __shfl(hit, gbase + best);
+                    const double wpm = shfld(pm, gbase + best);
+                    if (frame_ok && gl < L && SR.syndrome) SR.syndrome[frame * L + rank] = syn;
+                    if (frame_ok && gl == 0) {
+                        if (SR.hit) SR.hit[frame] = whit;
+                        if (P.st_metric) P.st_metric[frame] = wpm;
+                    }
+                }
                 if (frame_ok) {
                     if (gl < L) {
                         if (P.ls_metric) P.ls_metric[frame * L + rank] = pm;

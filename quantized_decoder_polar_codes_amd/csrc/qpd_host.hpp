@@ -226,6 +226,24 @@ class Engine {
         int32_t *chosen = nullptr;
     } list;
 
+    // Mask search (qpd_decode_search_host): while search.on is set, a decode runs the list
+    // epilogue without the candidate bits -- every path's CRC syndrome (the unmasked
+    // compare, collected: bit chk-1-j = check bit j XOR register bit crc_n-1-j) and metric
+    // in argsort(PML) order -- and the output path is the lowest rank whose syndrome equals
+    // one of the n words (the masks' register values >> crc_n - chk, qpd_search.hpp), the
+    // hit the lowest such index; none: rank 0 and -1.  n == 0: no output path, `out` NULL.
+    // The pointers but `words` are the frame's own ([L], [L], [1], [1]) and may be NULL;
+    // after the decode last_metric is the output path's metric, last_pass whether any hit.
+    struct SearchOut {
+        bool on = false;
+        const uint32_t *words = nullptr;
+        int n = 0;
+        uint32_t *syndrome = nullptr;
+        double *metric = nullptr;
+        int32_t *hit_mask = nullptr;
+        int32_t *hit_rank = nullptr;
+    } search;
+
     // One frame: y[N] (int32 symbols or float64 LLRs) -> out[out_k].
     // Returns 0, or qpd::ERR_SYMBOL for a channel symbol outside [0, v).
     template <class In>
@@ -249,7 +267,9 @@ class Engine {
         else
             run<true>();
         if (flags) return flags;  // NaN metric: the reference's sort is undefined there, stop
-        if (list.bits)
+        if (search.on)
+            finish_search(out);
+        else if (list.bits)
             finish_list(out);
         else if (out || !want_dmetric)
             finish(out);
@@ -730,6 +750,46 @@ class Engine {
         if (list.chosen) *list.chosen = chosen;
         last_metric = pm[idx[chosen]];
         if (out) std::memcpy(out, list.bits + (size_t)chosen * K, P.out_k);
+    }
+
+    // The search run (CRC-aided kinds, L <= 16): finish_list's walk with each path's
+    // syndrome in place of its K bits and verdict, and the set compare on it.
+    void finish_search(uint8_t *out) {
+        const int L = P.L, chk = P.ca_chk;
+        last_pass = false;
+        if (nan_key(pm.data(), L)) return;
+        std_sort_index(idx.data(), pm.data(), L);
+        int chosen = 0, hit = -1;
+        const uint32_t top = 1u << (P.crc_n - 1), mask = (top << 1) - 1u;
+        for (int r = 0; r < L; ++r) {
+            const uint64_t *x = reencode(idx[r]);
+            uint32_t reg = 0, syn = 0;
+            for (int t = 0; t < P.ca_A + chk; ++t) {
+                const uint32_t bt = bit(x, P.info_pos[t]);
+                if (t < P.ca_A) {
+                    const uint32_t fb = bt ^ ((reg & top) ? 1u : 0u);
+                    reg = ((reg << 1) & mask) ^ (P.crc_q & (0u - fb));
+                } else {
+                    const int j = t - P.ca_A;
+                    syn |= (bt ^ ((reg >> (P.crc_n - 1 - j)) & 1u)) << (chk - 1 - j);
+                }
+            }
+            if (search.syndrome) search.syndrome[r] = syn;
+            if (search.metric) search.metric[r] = pm[idx[r]];
+            for (int i = 0; i < search.n && hit < 0; ++i)
+                if (search.words[i] == syn) {
+                    hit = i;
+                    chosen = r;
+                }
+        }
+        last_pass = hit >= 0;
+        if (search.hit_mask) *search.hit_mask = hit;
+        if (search.hit_rank) *search.hit_rank = chosen;
+        last_metric = pm[idx[chosen]];
+        if (out) {
+            const uint64_t *x = reencode(idx[chosen]);
+            for (int t = 0; t < P.out_k; ++t) out[t] = bit(x, P.info_pos[t]);
+        }
     }
 };
 

@@ -32,7 +32,7 @@ from . import _lib
 from .lut import PackedLUT, pack_luts
 from .quant import LloydQuant, UniformQuant, pack_lloyd, pack_uniform
 
-__all__ = ["ChannelQuantizer", "DecodeStatus", "DecodeList", "SCDecoder", "SCLUTDecoder", "SCLLUTDecoder", "FastSCLUTDecoder", "FastSCLLUTDecoder",
+__all__ = ["ChannelQuantizer", "DecodeStatus", "DecodeList", "MaskSearch", "SCDecoder", "SCLUTDecoder", "SCLLUTDecoder", "FastSCLUTDecoder", "FastSCLLUTDecoder",
            "CASCLLUTDecoder", "CAFastSCLLUTDecoder", "SCLDecoder", "CASCLDecoder", "FastSCDecoder", "FastSCLDecoder",
            "SCUniformQuantizedDecoder", "SCLUniformQuantizedDecoder", "SCLloydQuantizedDecoder",
            "SCLLloydQuantizedDecoder"]
@@ -73,6 +73,22 @@ class DecodeList(NamedTuple):
     crc_pass: object
     chosen: object
     out: object
+
+
+class MaskSearch(NamedTuple):
+    """What ``decode_search_batch`` returns (qpd_decode_search, include/qpd.h): ``out`` (uint8
+    [B, A], the output path's bits), ``hit_mask`` (int32 [B]: the index of the mask that passed,
+    -1: none), ``hit_rank`` (int32 [B]: the output path's rank in the argsort of the path
+    metrics), ``metric`` (float64 [B], its metric), ``syndrome`` (uint32 [B, L]: every
+    candidate's CRC syndrome) and ``cand_metric`` (float64 [B, L]).  The first four are None for
+    an empty mask set.  numpy arrays or torch CUDA tensors."""
+
+    out: object
+    hit_mask: object
+    hit_rank: object
+    metric: object
+    syndrome: object
+    cand_metric: object
 
 
 def _torch():
@@ -341,6 +357,89 @@ class _DecoderBase:
         ty = _lib.QPD_IN_F64 if self._float_input else _lib.QPD_IN_U8 if u8 else _lib.QPD_IN_I32
         _lib.check(lib.qpd_decode_list_host(self._h, _ptr(a), ty, B, _ptr(out), ctypes.byref(la)))
         return DecodeList(bits, metric, None if flag is None else flag.astype(bool), chosen, out)
+
+    @staticmethod
+    def _mask_set(crc_masks, mask_bits):
+        """``crc_masks`` of ``decode_search_batch`` as a uint8 [R, bits] array of 0/1 rows."""
+        a = np.asarray(crc_masks)
+        if a.ndim == 2:
+            if mask_bits is not None and int(mask_bits) != a.shape[1]:
+                raise ValueError(f"crc_masks has rows of {a.shape[1]} bits, mask_bits = {mask_bits}")
+            if a.size and not ((a == 0) | (a == 1)).all():  # before the cast: 256 or 2.7 would become valid entries
+                raise ValueError("crc_masks entries must be 0 or 1")
+            return np.ascontiguousarray(a.astype(np.uint8))
+        bits = 16 if mask_bits is None else int(mask_bits)
+        if not 0 <= bits <= 32:
+            raise ValueError(f"mask_bits must be in [0, 32], got {bits}")
+        vals = [int(m) for m in a.reshape(-1)]
+        if any(m < 0 or m >> bits for m in vals):
+            raise ValueError(f"a mask does not fit {bits} bits")
+        rows = [[(m >> (bits - 1 - l)) & 1 for l in range(bits)] for m in vals]  # most significant bit first
+        return np.ascontiguousarray(np.array(rows, dtype=np.uint8).reshape(len(vals), bits))
+
+    def decode_search_batch(self, x, crc_masks, mask_bits=None):
+        """One list decode against a set of CRC masks (qpd_decode_search / _host) ->
+        :class:`MaskSearch`: which of the masks (e.g. the RNTIs a receiver holds), if any, a
+        frame is addressed to, and on which list path.  ``crc_masks``: an ``[R, bits]`` array
+        of 0/1 rows (each as ``crc_mask`` of ``decode_batch``), or a sequence of R ints of
+        ``mask_bits`` bits (default 16), most significant bit first; R <= 256.  The output path
+        is the lowest rank ``hit_rank`` (position in the argsort of the path metrics) that any
+        mask passes, ``hit_mask`` the lowest index that passes it (-1: none did, the output is
+        the best-metric path); ``out [B, A]`` and ``metric [B]`` are that path's.  ``syndrome
+        [B, L]`` (uint32) is every candidate's CRC syndrome -- the mask that would pass it,
+        cut to the compared bits -- and ``cand_metric [B, L]`` its metric.  An empty
+        ``crc_masks``: the syndromes and metrics alone (the other fields None).  numpy in ->
+        numpy out (synchronous); a torch CUDA tensor is read where it lies, on the current
+        stream -> torch CUDA tensors.  CRC-aided decoders with 2 <= L <= 16."""
+        torch = _torch()
+        lib = _lib.load()
+        masks = self._mask_set(crc_masks, mask_bits)
+        R = masks.shape[0]
+        sa = _lib.QpdSearchArgs()
+        sa.crc_masks, sa.n_masks, sa.crc_mask_bits = (_ptr(masks) if masks.size else None), R, masks.shape[1]
+        L = int(self.L)
+        if torch is not None and isinstance(x, torch.Tensor) and x.is_cuda:
+            u8 = not self._float_input and x.dtype == torch.uint8
+            want = torch.float64 if self._float_input else torch.uint8 if u8 else torch.int32
+            xs = x.reshape(-1, self.N).to(want).contiguous()
+            B = xs.shape[0]
+            dev = xs.device
+            syn = torch.empty((B, L), dtype=torch.int32, device=dev)  # (torch has no uint32 arithmetic: a view below)
+            cmet = torch.empty((B, L), dtype=torch.float64, device=dev)
+            out = hit = rank = metric = None
+            if R:
+                out = torch.empty((B, self.out_bits), dtype=torch.uint8, device=dev)
+                hit = torch.empty(B, dtype=torch.int32, device=dev)
+                rank = torch.empty(B, dtype=torch.int32, device=dev)
+                metric = torch.empty(B, dtype=torch.float64, device=dev)
+            p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+            sa.cand_syndrome, sa.cand_metric = p(syn), p(cmet)
+            sa.hit_mask, sa.hit_rank, sa.metric = p(hit), p(rank), p(metric)
+            ty = _lib.QPD_IN_F64 if self._float_input else _lib.QPD_IN_U8 if u8 else _lib.QPD_IN_I32
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.qpd_decode_search(self._h, ctypes.c_void_p(xs.data_ptr()), ty, B, p(out), ctypes.byref(sa),
+                                             ctypes.c_void_p(stream)))
+            return MaskSearch(out, hit, rank, metric, syn.view(torch.uint32), cmet)
+        if torch is not None and isinstance(x, torch.Tensor):
+            x = x.numpy()
+        a = np.asarray(x)
+        u8 = not self._float_input and a.dtype == np.uint8
+        want = np.float64 if self._float_input else np.uint8 if u8 else np.int32
+        a = np.ascontiguousarray(a.astype(want, copy=False).reshape(-1, self.N))
+        B = a.shape[0]
+        syn = np.zeros((B, L), dtype=np.uint32)
+        cmet = np.zeros((B, L), dtype=np.float64)
+        out = hit = rank = metric = None
+        if R:
+            out = np.zeros((B, self.out_bits), dtype=np.uint8)
+            hit = np.zeros(B, dtype=np.int32)
+            rank = np.zeros(B, dtype=np.int32)
+            metric = np.zeros(B, dtype=np.float64)
+        sa.cand_syndrome, sa.cand_metric = _ptr(syn), _ptr(cmet)
+        sa.hit_mask, sa.hit_rank, sa.metric = _ptr(hit), _ptr(rank), _ptr(metric)
+        ty = _lib.QPD_IN_F64 if self._float_input else _lib.QPD_IN_U8 if u8 else _lib.QPD_IN_I32
+        _lib.check(lib.qpd_decode_search_host(self._h, _ptr(a), ty, B, _ptr(out), ctypes.byref(sa)))
+        return MaskSearch(out, hit, rank, metric, syn, cmet)
 
     def decode_batch(self, x, return_status: bool = False, crc_mask=None):
         """Decode B frames.  numpy [B, N] -> numpy uint8 [B, K] (synchronous);
